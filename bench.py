@@ -13,6 +13,10 @@ list, followed by the all-gather of the match graph.
             descriptors are replicated, the pair list is dealt block-cyclically, the match graph
             is all-gathered over RCCL at the end of every step
   "ba"    : the second half of the metric (LM iterations / s of global BA), 1 GPU, rank 0 only
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and nothing else.  --full adds what is
+measured beside it (the one-GPU exchange emulation, the secondary workloads, "ba", the CPU baselines and their parity checks).
+--dump-outputs DIR writes the last timed step's match graph (counts.npy, matches.npy) so that two builds can be compared.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ PMC_FILE = os.path.join(ROOT, "profiles", "r06_match_pmc.json")  # HBM bytes per
 PMC_KERNEL = "match_fused_kernel"  # the kernel the roofline block is about: a counter file taken on another kernel is refused, not quoted
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -66,12 +70,20 @@ def parse():
     ap.add_argument("--no-guided", action="store_true", help="skip the guided-matching workload")
     ap.add_argument("--no-hahog", action="store_true", help="skip the HAHOG extraction workload")
     ap.add_argument("--full-parity", action="store_true", help="check EVERY pair with matches + 5000 empties against the oracle (~1.5 min)")
-    ap.add_argument("--headline-only", action="store_true", help="only the headline workload + its cpu_baseline (configs[3] runs)")
+    ap.add_argument("--headline-only", action="store_true", help="only the headline workload (+ its cpu_baseline with --full: configs[3] runs)")
     ap.add_argument("--all-sections", action="store_true", help="N > 1: also run the one-GPU secondary workloads and CPU baselines on rank 0")
     ap.add_argument("--emulate-world", type=int, default=8, help="N = 1: size of the emulated exchange step (exchange_emulation section; 0 = skip)")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also every section beside the headline figure: exchange emulation, secondary workloads, "
+                                                        "BA, CPU baselines and parity checks (a plain run times the headline workload only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's match graph as DIR/<name>.npy (float32)")
+    a = ap.parse_args(argv)
     if a.headline_only:
         a.no_ba = a.no_tracks = a.no_overlap = a.no_calibrated = a.no_float = a.no_guided = a.no_hahog = True
+    if not a.full:
+        if a.full_parity or a.all_sections:
+            ap.error("--full-parity and --all-sections are parts of --full")
+        a.no_ba = a.no_tracks = a.no_overlap = a.no_calibrated = a.no_float = a.no_guided = a.no_hahog = a.no_cpu_baseline = True
+        a.emulate_world = 0
     return a
 
 
@@ -194,6 +206,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0 and graph is not None:
+        dump_outputs(args.dump_outputs, {"counts": graph[0], "matches": graph[1]})
     total_pairs = len(pairs_all) * args.steps
     value = total_pairs / elapsed
 
@@ -307,7 +321,7 @@ def main():
                 out[name] = {"error": f"{type(exc).__name__}: {exc}", "traceback": traceback.format_exc()[-1500:]}
 
         if headline_only_for_ranks(args, world):
-            out["note"] = "secondary workloads and cpu_baseline are measured at N = 1 (python bench.py); --all-sections repeats them on rank 0"
+            out["note"] = "secondary workloads and cpu_baseline are measured at N = 1 (python bench.py --full); --all-sections repeats them on rank 0"
         if world == 1 and args.emulate_world > 1 and not args.headline_only:
             section("exchange_emulation", exchange_emulation, args, store, my_pairs, local_rank, robust, out["ms_per_step"])
         if not args.no_overlap:
@@ -341,6 +355,28 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path: str, arrays: dict, seed: int = 0) -> None:
+    """--dump-outputs: what the timed path handed its caller in the last step, one DIR/<name>.npy per array, as float32 (counts and
+    feature indices are far below 2^24: exact).  An array whose rows do not fit its share of DUMP_BYTES is replaced by a fixed, seeded
+    sample of its rows, in order, and DIR/<name>_rows.npy (float64) says which rows they are."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float32)
+        a = a.reshape(len(a), -1) if a.ndim > 1 else a
+        if os.path.exists(os.path.join(path, f"{name}_rows.npy")):  # (an earlier run's sample into the same DIR)
+            os.remove(os.path.join(path, f"{name}_rows.npy"))
+        if a.nbytes > share:
+            row_bytes = a.nbytes // len(a) + 8
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), share // row_bytes, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def exchange_emulation(args, store, my_pairs, local_rank, robust, ms_per_step_n1, reps: int = 5):

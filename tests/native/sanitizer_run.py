@@ -1,8 +1,9 @@
 """Driven by tests/test_native_sanitizers.py in a subprocess with libasan preloaded: runs the host-compiled kernel code
 (relpose_core.h / relpose_rounds.h / guided_wave.h) built with -fsanitize=address,undefined over small and degenerate
 inputs, every speculation width, single pairs and batches.  argv: the two sanitized shared objects."""
-import ctypes as C, numpy as np, sys
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import ctypes as C, numpy as np, os, sys
+TESTS=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,os.path.dirname(TESTS)); sys.path.insert(0,TESTS)
 import test_relpose_core_host as rp
 import test_guided_host as gh
 host=C.CDLL(sys.argv[1])

@@ -58,21 +58,39 @@ def test_signatures_follow_the_pybind_definitions():
                                                                                                     "min_common_points", "max_interior_size"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is not mounted")
-def test_names_exist_in_the_references_bindings():
-    """every name this package provides is a name the reference's pybind.cc defines (read from the file)"""
-    def defined(path, pattern):
-        return set(re.findall(pattern, open(os.path.join(REF, path)).read()))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "binding_names.json")
 
-    feat = defined("features/python/pybind.cc", r'm\.def\("(\w+)"')
+
+def binding_names(ref: str) -> dict:
+    """the names the reference's pybind.cc files define and the functions its bundle_adjuster.h declares, read from the files
+    (tests/golden/gen_binding_names.py stores them in tests/golden/binding_names.json)"""
+    def defined(path, pattern):
+        return sorted(set(re.findall(pattern, open(os.path.join(ref, path)).read())))
+
+    return {"features_def": defined("features/python/pybind.cc", r'm\.def\("(\w+)"'),
+            "robust_def": defined("robust/python/pybind.cc", r'm\.def\("(\w+)"'),
+            "robust_quoted": defined("robust/python/pybind.cc", r'"(\w+)"'),
+            "sfm_def_static": defined("sfm/python/pybind.cc", r'def_static\("(\w+)"'),
+            "bundle_def": defined("bundle/python/pybind.cc", r'\.def\("(\w+)"'),
+            "bundle_adjuster_h_calls": defined("bundle/bundle_adjuster.h", r"\b(\w+)\s*\(")}
+
+
+def test_names_exist_in_the_references_bindings():
+    """every name this package provides is a name the reference's pybind.cc defines (the stored lists; read from the files where the
+    reference is present, and then the stored lists must be what the files hold)"""
+    import json
+
+    names = json.load(open(GOLDEN))
+    if os.path.isdir(REF):
+        assert binding_names(REF) == names, "tests/golden/binding_names.json is stale: run tests/golden/gen_binding_names.py"
+    feat = set(names["features_def"])
     assert {"hahog", "match_using_words", "compute_vlad_descriptor", "compute_vlad_distances"} <= feat
-    rob = open(os.path.join(REF, "robust/python/pybind.cc")).read()
-    assert 'm.def("ransac_relative_pose"' in rob and '"RobustEstimatorParams"' in rob and '"RansacType"' in rob
+    assert "ransac_relative_pose" in names["robust_def"] and {"RobustEstimatorParams", "RansacType"} <= set(names["robust_quoted"])
     for field in ("iterations", "probability", "use_local_optimization", "use_iteration_reduction", "score", "model", "lo_model", "inliers_indices"):
-        assert f'"{field}"' in rob
-    sfm = defined("sfm/python/pybind.cc", r'def_static\("(\w+)"')
+        assert field in names["robust_quoted"]
+    sfm = set(names["sfm_def_static"])
     assert {"bundle", "bundle_local", "bundle_shot_poses", "shot_neighborhood_ids", "bundle_to_map", "detect_alignment_constraints", "add_gcp_to_bundle"} <= sfm
-    bundle_methods = defined("bundle/python/pybind.cc", r'\.def\("(\w+)"')
+    bundle_methods = set(names["bundle_def"])
     ours = {n for n, f in inspect.getmembers(compat.pybundle.BundleAdjuster, callable) if not n.startswith("_")}
     needed = {"run", "add_camera", "get_camera", "add_rig_camera", "get_rig_camera_pose", "add_rig_instance", "get_rig_instance_pose",
               "add_rig_instance_position_prior", "add_point", "add_point_prior", "get_point", "has_point", "add_point_projection_observation",
@@ -81,7 +99,7 @@ def test_names_exist_in_the_references_bindings():
               "set_use_analytic_derivatives", "set_linear_solver_type", "brief_report", "full_report"}
     assert needed <= bundle_methods and needed <= ours, sorted(needed - ours)
     # what the class has beyond the Python bindings are methods sfm::BAHelpers calls on the C++ object (bundle_adjuster.h), in snake case
-    header = open(os.path.join(REF, "bundle/bundle_adjuster.h")).read()
+    header_calls = set(names["bundle_adjuster_h_calls"])
     for extra in ours - bundle_methods:
         camel = "".join(w.capitalize() for w in extra.split("_")).replace("Sd", "SD")
-        assert re.search(r"\b" + camel + r"\s*\(", header), (extra, camel)
+        assert camel in header_calls, (extra, camel)

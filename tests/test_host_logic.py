@@ -223,3 +223,48 @@ def test_bench_line_at_n_above_one_is_the_headline_workload_only():
     assert bench.headline_only_for_ranks(a, 8) and all(getattr(a, f) for f in flags)
     b = types.SimpleNamespace(all_sections=True, **{f: False for f in flags})
     assert not bench.headline_only_for_ranks(b, 8) and not any(getattr(b, f) for f in flags)
+
+
+def test_bench_plain_run_is_the_headline_only_and_full_keeps_every_section():
+    """a plain bench.py run times the headline workload and prints its line; --full runs every section a run did before it existed"""
+    import importlib
+    import os
+    import sys
+
+    import pytest
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    flags = ("no_ba", "no_tracks", "no_overlap", "no_calibrated", "no_float", "no_guided", "no_hahog", "no_cpu_baseline")
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.steps, plain.warmup) == (7, 2) and all(getattr(plain, f) for f in flags) and plain.emulate_world == 0
+    full = bench.parse(["--full"])
+    assert not any(getattr(full, f) for f in flags) and full.emulate_world == 8
+    assert bench.parse(["--full", "--no-hahog"]).no_hahog and not bench.parse(["--full", "--no-hahog"]).no_ba
+    with pytest.raises(SystemExit):
+        bench.parse(["--full-parity"])
+
+
+def test_bench_dump_outputs_are_exact_float32_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array, float32, the same values; above the budget a seeded sample of rows and their indices"""
+    import importlib
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(3)
+    counts = rng.integers(0, 2000, 50000).astype(np.int32)
+    matches = rng.integers(0, 2000, (int(counts.sum()) // 100, 2)).astype(np.int32)
+    bench.dump_outputs(str(tmp_path), {"counts": counts, "matches": matches})
+    c, m = np.load(tmp_path / "counts.npy"), np.load(tmp_path / "matches.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, counts) and m.shape == matches.shape and np.array_equal(m, matches)
+    assert not (tmp_path / "matches_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * counts.nbytes)  # the matches no longer fit their half
+    for _ in range(2):  # the same rows every time
+        bench.dump_outputs(str(tmp_path), {"counts": counts, "matches": matches})
+        rows, m = np.load(tmp_path / "matches_rows.npy"), np.load(tmp_path / "matches.npy")
+        assert np.all(np.diff(rows) > 0) and np.array_equal(m, matches[rows.astype(np.int64)])
+        assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= bench.DUMP_BYTES + 4 * 128
+    bench.dump_outputs(str(tmp_path), {"counts": counts})
+    assert not (tmp_path / "counts_rows.npy").exists()

@@ -8,7 +8,7 @@ OUT=/root/repo/gpurun_out/${TAG}_records
 mkdir -p $OUT
 cd /root/repo
 python -c "import oracle; oracle.build()" > $OUT/oracle_build.log 2>&1
-timeout 600 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc $?"; tail -c 300 $OUT/${TAG}_bench.json; echo
+timeout 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err; echo "bench rc $?"; tail -c 300 $OUT/${TAG}_bench.json; echo
 timeout 600 python -m pytest tests -m gpu -q --durations=8 -s > $OUT/${TAG}_pytest_gpu.txt 2>&1; echo "pytest rc $?"; tail -3 $OUT/${TAG}_pytest_gpu.txt
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/headline -o headline -- python /root/repo/bench.py --headline-only --no-cpu-baseline > $OUT/headline.json 2> $OUT/headline.err
