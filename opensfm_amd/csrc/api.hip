@@ -432,8 +432,7 @@ static int match_pairs_impl(osfm_ctx *ctx, const osfm_store *store, const int32_
   }
   OSFM_REQUIRE(ok, OSFM_E_NOMEM, "hipMalloc failed for match buffers: %s", hipGetErrorString(e));
   if (!ctx->stream_b) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-  // measurement knob: OSFM_MATCH_ONE_STREAM=1 puts everything on the matcher's stream (no overlap between chunks)
-  hipStream_t stA = ctx->stream, stB = getenv("OSFM_MATCH_ONE_STREAM") ? ctx->stream : ctx->stream_b;
+  hipStream_t stA = ctx->stream, stB = ctx->stream_b;
   // The fundamental-matrix RANSAC runs on the MATCHER's stream, right behind its chunk: the matcher owns every SIMD's registers and
   // nearly all LDS (2 x 78 KiB per CU), so kernels of a second stream only get in where a matcher workgroup retires -- measured on the
   // neighbour list, the robust stage takes 1.0 ms on its own and 9 ms of stream time underneath the matcher, which it slows down in

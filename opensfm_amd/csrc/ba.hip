@@ -32,30 +32,15 @@ namespace {
 
 constexpr int kCoopObs = 256;  // observations per workgroup of the cooperative per-track kernels (mat-vec, point gradient)
 
-// Streaming stores (round 6): the Jacobian rows are written once by the evaluation and read much later by other kernels, 680 MB that no cache
-// holds -- written past the caches (`nt`) they cost 3 % of an LM iteration less (3.08 -> 3.00 ms at configs[4], profiles/r06_ba_variants2.json).
-// OSFM_BA_NT_LEVEL (build knob): 0 none, 1 the evaluation's rows (default), 2 every streaming store (the E blocks, w, the border's w), 3 also the
-// streaming LOADS of the rows -- levels 2 and 3 measured level with 1 (profiles/r06_ba_variants3.json: w is read back by the very next kernel)
-#ifndef OSFM_BA_NT_LEVEL
-#define OSFM_BA_NT_LEVEL 1
-#endif
+// The evaluation writes the Jacobian rows past the caches (round 6): they are read much later by other kernels, 680 MB that no cache holds -- 3 % of
+// an LM iteration less (3.08 -> 3.00 ms at configs[4], profiles/r06_ba_variants2.json).  Non-temporal stores of the E blocks and w and non-temporal
+// loads of the rows measured level with plain ones (profiles/r06_ba_variants3.json: w is read back by the very next kernel): st2 is a plain store.
 typedef double osfm_v2d __attribute__((ext_vector_type(2)));
-template <int LEVEL>
-__device__ __forceinline__ void st_stream(double *p, double v) {
-  if (OSFM_BA_NT_LEVEL >= LEVEL) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
-template <int LEVEL>
-__device__ __forceinline__ void st_stream2(double *p, double a, double b) {  // p: 16-byte aligned
+__device__ __forceinline__ void st2(double *p, double a, double b) {  // p: 16-byte aligned
   osfm_v2d v;
   v.x = a;
   v.y = b;
-  if (OSFM_BA_NT_LEVEL >= LEVEL) __builtin_nontemporal_store(v, reinterpret_cast<osfm_v2d *>(p));
-  else *reinterpret_cast<osfm_v2d *>(p) = v;
-}
-__device__ __forceinline__ double ld_stream(const double *p) {
-  if (OSFM_BA_NT_LEVEL >= 3) return __builtin_nontemporal_load(p);
-  return *p;
+  *reinterpret_cast<osfm_v2d *>(p) = v;
 }
 
 // the six entries of Jk (d residual / d [k1 k2 focal]) from the point (u, v) of the undistorted image plane.  ONE function for the evaluation and
@@ -323,7 +308,6 @@ struct Dev {
   const int *bp_o0, *bp_last;   // P: first observation (point-major position) and last shot offset (from the first shot) of the sorted points
   const unsigned char *bp_pos;  // P x 16: which observation of the sorted point sits at shot offset 0 .. 15 (255: the track misses that shot)
   const int *bp_off;            // S + 1: first sorted position of every anchor
-  int bpMode;                   // measurement knob (OSFM_BA_BM_MODE): 1 = no products, 2 = every load from row 0
   int bpNT, bpR, bpPC;          // 16-row tiles of an anchor's matrix, parts per anchor, points per staged chunk
   double *bp_part;              // (S * bpR) x (bpNT (bpNT + 1) / 2) x 256: every workgroup's accumulator tiles
   // cluster block-tridiagonal form of the same band (cs >= bw shots per cluster, dense ncd x ncd blocks)
@@ -347,7 +331,6 @@ struct Dev {
   double *qx, *qy;   // right-hand sides (down sweep, in place) and results (up sweep), (qN qm) x NR, NR side by side
   int qT;            // panel width of the blocked inversion (<= 96, a multiple of 6)
   double *qP, *qR, *qRn, *qC;  // per cluster of a level: pivot block inverse (qT^2), row panel, P x row panel (qT x qm), column panel (qm x qT)
-  double *qP2, *qBn;           // look-ahead: the next panel's pivot inverse (the two alternate) and its pivot block before the trailing product
   double *zc;       // nred (unscaled J^T w)
   double *y;        // nred
   // pcg
@@ -363,7 +346,6 @@ struct Dev {
 };
 
 #define JA(o, c) d.Jpm[(long)(c) * d.M + (o)]  /* point-major SoA */
-#define JL(o, c) ld_stream(&d.Jpm[(long)(c) * d.M + (o)])  /* ... a row's component read once by a streaming pass */
 // Components of a point-major row (round 6: 17; rounds 1-5 stored 26 -- 208 bytes per observation through a write path that sustains ~2.5 TB/s
 // here).  The translation columns of Jc are -Jp; the six entries of Jk follow from (u, v), the robust weight, sigma and the camera (row_jk:
 // project_obs's own expressions): neither is stored.  res 2 | Jp 2 x 3 | Jr 2 x 3 (the ROTATION columns of Jc) | u | v | wt
@@ -373,7 +355,7 @@ constexpr int R_JP = 2, R_JR = 8, R_U = 14, R_V = 15, R_WT = 16;
 // Jk of the observation at point-major position o (of shot s), times the robust weight, from what its row keeps
 __device__ __forceinline__ void row_jk(const Dev &d, long o, int s, double (&jk)[6]) {
   const int ci = d.shot_camera[s];
-  const double u = JL(o, R_U), v = JL(o, R_V), wt = JL(o, R_WT), sg = d.o_sigma[o];
+  const double u = JA(o, R_U), v = JA(o, R_V), wt = JA(o, R_WT), sg = d.o_sigma[o];
   const double *cam = d.cams + 3 * ci;
   const double k1 = cam[0], k2 = cam[1], f = cam[2];
   const bool other = d.cam_model && d.cam_model[ci] >= 2;  // a constant camera of another model: no [k1 k2 focal] columns
@@ -479,9 +461,8 @@ __global__ void __launch_bounds__(kCoopObs) eval_kernel(Dev d, const double *cam
     v[8] = jp[2] * jp[2] + jp[5] * jp[5];
   };
   auto store = [&](long o, const double (&row)[kRowComps]) {
-    if (d.bpMode == 3) return;  // measurement knob (OSFM_BA_BM_MODE=3): the evaluation without its row stores (results are garbage)
 #pragma unroll
-    for (int i = 0; i < kRowComps; i++) st_stream<1>(&JA(o, i), row[i]);
+    for (int i = 0; i < kRowComps; i++) __builtin_nontemporal_store(row[i], &JA(o, i));
     if (d.Epm) {  // E_o = Jc_o^T Jp_o (6 x 3) of the corrected blocks, 144 contiguous bytes per observation: the per-shot band assembly's operand
       const double *jp = row + R_JP;
       double2 *dst = reinterpret_cast<double2 *>(d.Epm + 18 * o);
@@ -495,9 +476,9 @@ __global__ void __launch_bounds__(kCoopObs) eval_kernel(Dev d, const double *cam
           e[j] = a0 * jp[j] + b0 * jp[3 + j];
           e[3 + j] = a1 * jp[j] + b1 * jp[3 + j];
         }
-        st_stream2<2>(reinterpret_cast<double *>(dst + 3 * (i / 2)), e[0], e[1]);
-        st_stream2<2>(reinterpret_cast<double *>(dst + 3 * (i / 2) + 1), e[2], e[3]);
-        st_stream2<2>(reinterpret_cast<double *>(dst + 3 * (i / 2) + 2), e[4], e[5]);
+        st2(reinterpret_cast<double *>(dst + 3 * (i / 2)), e[0], e[1]);
+        st2(reinterpret_cast<double *>(dst + 3 * (i / 2) + 1), e[2], e[3]);
+        st2(reinterpret_cast<double *>(dst + 3 * (i / 2) + 2), e[4], e[5]);
       }
     }
   };
@@ -1205,7 +1186,7 @@ __global__ void __launch_bounds__(384) band_mfma_kernel(Dev d) {
     int n_p, n_o0, n_k;
     auto fetch_index = [&](int c) {
       const bool on = loader && c + ut < i1;
-      const long r = d.bpMode == 2 ? 0 : on ? c + ut : i0 < i1 ? i0 : 0;
+      const long r = on ? c + ut : i0 < i1 ? i0 : 0;
       n_p = d.bp_pts[r];
       n_o0 = d.bp_o0[r];
       const int k = d.bp_pos[16 * r + ush];
@@ -1290,7 +1271,7 @@ __global__ void __launch_bounds__(384) band_mfma_kernel(Dev d) {
         ia[m] = bo + 18 * kBmStride + (adA[m] < 0 ? kBmSlots : adA[m]);
         ib[m] = bo + (adB[m] < 0 ? kBmSlots : adB[m]);
       }
-      for (int t = 0; t < (d.bpMode == 1 ? 0 : npt); t++) {
+      for (int t = 0; t < npt; t++) {
         double va[MAXT], vb[MAXT];
 #pragma unroll
         for (int m = 0; m < MAXT; m++) {
@@ -1723,12 +1704,6 @@ __device__ __forceinline__ void inv6_spd(double (&a)[6][6], int &bad) {
     }
   }
 }
-#ifdef OSFM_BCR_UBENCH
-__device__ int osfm_bcr_variant;
-#define OSFM_BCR_SKIP(bit) (osfm_bcr_variant & (bit))
-#else
-#define OSFM_BCR_SKIP(bit) false
-#endif
 template <int CS>
 struct BcrShape {
   static constexpr int n = 6 * CS, W = 3 * n, n2 = n * n;
@@ -1756,11 +1731,6 @@ __global__ void __launch_bounds__(BcrShape<CS>::threads) bcr_level_kernel(Dev d,
     for (int u = 0; u < NL; u++) {
       const int t = tid + u * T;
       const bool in = t < n2;
-      if (OSFM_BCR_SKIP(8)) {
-        vD[u] = (t / n == t % n) ? 4.0 : 0.01;
-        vE[u] = vR[u] = 0.02;
-        continue;
-      }
       vD[u] = in ? gD[t] + gD2[t] : 0.0;
       vE[u] = (in && hasL) ? gEi[t] : 0.0;
       vR[u] = (in && hasR) ? gEr[t] : 0.0;
@@ -1790,7 +1760,7 @@ __global__ void __launch_bounds__(BcrShape<CS>::threads) bcr_level_kernel(Dev d,
       for (int c = 0; c < 6; c++) own[r][c] = Aug[(6 * tr + r) * W + 6 * tq + c];
   }
 #pragma unroll 1
-  for (int k = OSFM_BCR_SKIP(1) ? CS : 0; k < CS; k++) {
+  for (int k = 0; k < CS; k++) {
     if (has_tile) {
       double nr[6][6];  // the pivot block row after scaling, this tile's columns (the pivot block itself becomes Pinv)
       {
@@ -1845,23 +1815,21 @@ __global__ void __launch_bounds__(BcrShape<CS>::threads) bcr_level_kernel(Dev d,
     __syncthreads();
   }
   if (bad) *status = 1;
-  if (!OSFM_BCR_SKIP(2)) {
-    double *oD = d.bD + (long)i * n2, *oG = d.bG + (long)i * n2, *oH = d.bH + (long)i * n2;
-    double *oGt = d.bGt + (long)i * n2, *oHt = d.bHt + (long)i * n2;
-    for (int t = tid; t < n2; t += T) {
-      const int r = t / n, c = t - r * n;
-      oD[t] = Aug[r * W + c];
-      if (hasL) {
-        oG[t] = Aug[r * W + n + c];
-        oGt[t] = Aug[c * W + n + r];
-      }
-      if (hasR) {
-        oH[t] = Aug[r * W + 2 * n + c];
-        oHt[t] = Aug[c * W + 2 * n + r];
-      }
+  double *oD = d.bD + (long)i * n2, *oG = d.bG + (long)i * n2, *oH = d.bH + (long)i * n2;
+  double *oGt = d.bGt + (long)i * n2, *oHt = d.bHt + (long)i * n2;
+  for (int t = tid; t < n2; t += T) {
+    const int r = t / n, c = t - r * n;
+    oD[t] = Aug[r * W + c];
+    if (hasL) {
+      oG[t] = Aug[r * W + n + c];
+      oGt[t] = Aug[c * W + n + r];
+    }
+    if (hasR) {
+      oH[t] = Aug[r * W + 2 * n + c];
+      oHt[t] = Aug[c * W + 2 * n + r];
     }
   }
-  if (root || OSFM_BCR_SKIP(4)) return;
+  if (root) return;
   // the three products for the neighbours: CS x CS tiles each, one per thread; the results go through LDS (the augmented array is
   // free by then) so that the read-modify-write of the neighbours' blocks is coalesced
   const int which = tid / (CS * CS), tl = tid - which * (CS * CS), pr = tl / CS, pc = tl - pr * CS;
@@ -2149,6 +2117,8 @@ inline BcrLaunch bcr_level_for(int cs) {
 // its 3 x 3 quarters (adjugates, two divisions instead of six: 97 -> 93 us, and the facade's two-shot scene with weak priors lost three digits).
 constexpr int kSbThreads = 256;
 constexpr size_t kSbLdsMax = 160 * 1024 - 512;
+constexpr int kSbMaxBw = 10;  // widest band it handles: the window's (a, b) block pairs fit pair_a / pair_b[64], lane 6 (a - 1) + r the rows of L_(., j)
+static_assert(kSbMaxBw * (kSbMaxBw + 1) / 2 - 1 <= 64 && 6 * kSbMaxBw <= 64, "sband_factor_kernel's tables and lane mapping");
 constexpr int kSbSolveWaves = 4;  // right-hand sides per workgroup of the solve (a wavefront each, one copy of the factor in LDS)
 inline size_t sband_factor_lds(int S, int bw) { return ((size_t)S * (bw + 1) * 36 + (size_t)2 * bw * 36 + (size_t)6 * S) * sizeof(double); }
 inline size_t sband_solve_lds(int S, int bw) { return ((size_t)S * (bw + 1) * 36 + (size_t)kSbSolveWaves * 6 * S) * sizeof(double); }
@@ -2914,92 +2884,6 @@ __global__ void __launch_bounds__(256) dgj_scatter_kernel(double *A0, long strid
   const int c = (int)(t / w), r = (int)(t - (long)c * w);
   A[(long)c * m + j0 + r] = (c >= j0 && c < j0 + w) ? P[(long)(c - j0) * T + r] : Rn[(long)c * T + r];
 }
-// ---- the same inversion with the pivot chain taken off the trailing product (look-ahead) ----
-// Of everything panel J + 1 needs from panel J's trailing product A -= C R', only its own pivot block is on the critical path: it is
-// B - C[rows J + 1] R'[:, columns J + 1], a 96^3 product.  dgj_copy_kernel saves that block (B) with the panels before the products of
-// panel J start; as soon as R' exists, dgj_pivot_ahead_kernel forms the updated block itself, inverts it on a second stream and hands
-// P_{J+1} over with an event, while the main stream runs the three products and the scatter of panel J.
-__global__ void __launch_bounds__(256) dgj_copy_kernel(const double *A0, long strideA, int m, int T, int j0, int w, int jn, int wn, double *R0, double *C0,
-                                                       double *B0) {
-  const double *A = A0 + (long)blockIdx.y * strideA;
-  double *R = R0 + (long)blockIdx.y * T * m, *C = C0 + (long)blockIdx.y * T * m, *B = B0 + (long)blockIdx.y * T * T;
-  const long n = (long)w * m, nth = (long)gridDim.x * 256;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += nth) {
-    {
-      const int c = (int)(t / w), r = (int)(t - (long)c * w);
-      R[(long)c * T + r] = A[(long)c * m + j0 + r];
-    }
-    {
-      const int c = (int)(t / m), r = (int)(t - (long)c * m);
-      C[(long)c * m + r] = (r >= j0 && r < j0 + w) ? 0.0 : A[(long)(j0 + c) * m + r];
-    }
-    if (t < (long)wn * wn) {
-      const int c = (int)(t / wn), r = (int)(t - (long)c * wn);
-      B[(long)c * T + r] = A[(long)(jn + c) * m + jn + r];
-    }
-  }
-}
-// first: the pivot block is A's own (panel 0 of a level); else B - C[rows jn ..] R'[:, columns jn ..] with the panels of width w before it
-__global__ void __launch_bounds__(256) dgj_pivot_ahead_kernel(const double *A0, long strideA, int m, int T, int first, int w, int jn, int wn, const double *C0,
-                                                              const double *Rn0, const double *B0, double *P0, int *status) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double *X = lds, *Z = lds + kWB * kWLd;
-  const int tid = threadIdx.x;
-  if (first) {
-    const double *A = A0 + (long)blockIdx.y * strideA;
-    for (int t = tid; t < kWB * kWB; t += 256) {
-      const int c = t / kWB, r = t - c * kWB;
-      X[r * kWLd + c] = (r < wn && c < wn) ? A[(long)(jn + c) * m + jn + r] : (r == c ? 1.0 : 0.0);
-    }
-  } else {
-    const double *C = C0 + (long)blockIdx.y * T * m, *Rn = Rn0 + (long)blockIdx.y * T * m, *B = B0 + (long)blockIdx.y * T * T;
-    for (int t = tid; t < kWB * kWB; t += 256) {
-      const int k = t / kWB, r = t - k * kWB;  // X[r][k] = C(jn + r, k): consecutive threads along a column of C
-      X[r * kWLd + k] = (r < wn && k < w) ? C[(long)k * m + jn + r] : 0.0;
-    }
-    for (int t = tid; t < kWB * kWB; t += 256) {
-      const int c = t / kWB, k = t - c * kWB;  // Z[k][c] = R'(k, jn + c)
-      Z[k * kWLd + c] = (k < w && c < wn) ? Rn[(long)(jn + c) * T + k] : 0.0;
-    }
-    __syncthreads();
-    constexpr int NT = kWB / 6;
-    const int tr = tid / NT, tq = tid - tr * NT;
-    double acc[6][6];
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int b = 0; b < 6; b++) acc[a][b] = 0.0;
-#pragma unroll 2
-    for (int k = 0; k < kWB; k++) {
-      double x[6], y[6];
-#pragma unroll
-      for (int a = 0; a < 6; a++) x[a] = X[(6 * tr + a) * kWLd + k];
-#pragma unroll
-      for (int b = 0; b < 6; b++) y[b] = Z[k * kWLd + 6 * tq + b];
-#pragma unroll
-      for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int b = 0; b < 6; b++) acc[a][b] = __builtin_fma(x[a], y[b], acc[a][b]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int b = 0; b < 6; b++) {
-        const int r = 6 * tr + a, c = 6 * tq + b;
-        X[r * kWLd + c] = (r < wn && c < wn) ? B[(long)c * T + r] - acc[a][b] : (r == c ? 1.0 : 0.0);
-      }
-  }
-  __syncthreads();
-  int bad = 0;
-  wide_gj_inverse_mfma(X, Z, tid, bad, (wn + 15) / 16);  // (Z held an operand of the product: free by now)
-  if (bad) status[2] = 1;
-  double *P = P0 + (long)blockIdx.y * T * T;
-  for (int t = tid; t < wn * wn; t += 256) {
-    const int c = t / wn, r = t - c * wn;
-    P[(long)c * T + r] = X[r * kWLd + c];
-  }
-}
 // dst_(k, w) = src_(k, w)^T for m x m column-major blocks; block (k, w) at base + k * stride_k + w * stride_w; 32 x 32 tiles through LDS
 __global__ void __launch_bounds__(256) dbcr_transpose_kernel(const double *src, long src_k, long src_w, double *dst, long dst_k, long dst_w, int m, int nw) {
   __shared__ double tile[32][33];
@@ -3228,8 +3112,8 @@ __global__ void __launch_bounds__(kCoopObs) schur_point_coop_kernel(Dev d, const
 #pragma unroll
     for (int j = 0; j < 3; j++) {
       const double yj = ys[j];
-      t0 += JL(o, R_JR + j) * yj;
-      t1 += JL(o, R_JR + 3 + j) * yj;
+      t0 += JA(o, R_JR + j) * yj;
+      t1 += JA(o, R_JR + 3 + j) * yj;
     }
 #pragma unroll
     for (int j = 0; j < 3; j++) {
@@ -3251,7 +3135,7 @@ __global__ void __launch_bounds__(kCoopObs) schur_point_coop_kernel(Dev d, const
     if (tid < nobs) {
       pl = d.o_point[o] - p0;
 #pragma unroll
-      for (int j = 0; j < 6; j++) jp[j] = JL(o, R_JP + j);
+      for (int j = 0; j < 6; j++) jp[j] = JA(o, R_JP + j);
       if (MODE != 1) {
         row_t(o, jp, t0, t1);
 #pragma unroll
@@ -3302,7 +3186,7 @@ __global__ void __launch_bounds__(kCoopObs) schur_point_coop_kernel(Dev d, const
     }
     if (tid < nobs) {
       const double v0 = vpt[3 * pl], v1 = vpt[3 * pl + 1], v2 = vpt[3 * pl + 2];
-      st_stream2<2>(d.w + 2 * o, t0 - (jp[0] * v0 + jp[1] * v1 + jp[2] * v2), t1 - (jp[3] * v0 + jp[4] * v1 + jp[5] * v2));
+      st2(d.w + 2 * o, t0 - (jp[0] * v0 + jp[1] * v1 + jp[2] * v2), t1 - (jp[3] * v0 + jp[4] * v1 + jp[5] * v2));
     }
     return;
   }
@@ -3722,10 +3606,6 @@ __global__ void reproj_kernel(Dev d, double *out) {
 // border is eliminated exactly instead:  W = A^-1 B (nb cyclic-reduction solves),  Sigma = C - B^T W,
 //   z_s = A^-1 r_s,   z_c = Sigma^-1 (r_c - B^T z_s),   z_s -= W z_c,
 // which makes the preconditioner the reduced matrix itself: CG converges in one or two iterations.
-__global__ void unit_vec_kernel(double *x, int n, int j) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] = i == j ? 1.0 : 0.0;
-}
 // out[i * nb + j] = Bc_i . W_j   (one block per entry)
 __global__ void border_dots_kernel(const double *Bc, const double *W, int nb, int n, double *out) {
   __shared__ double lds[32];
@@ -3848,7 +3728,7 @@ __global__ void __launch_bounds__(kCoopObs) border_point_kernel(Dev d, double *w
         t1[k] = jk[3 + k] * sck[k];
       }
 #pragma unroll
-      for (int j = 0; j < 6; j++) jp[j] = JL(o, R_JP + j);
+      for (int j = 0; j < 6; j++) jp[j] = JA(o, R_JP + j);
 #pragma unroll
       for (int k = 0; k < 3; k++)
 #pragma unroll
@@ -3887,7 +3767,7 @@ __global__ void __launch_bounds__(kCoopObs) border_point_kernel(Dev d, double *w
       for (int c = 0; c < NB; c++) {
         const double v0 = vpt[(3 * pl + 0) * NB + c], v1 = vpt[(3 * pl + 1) * NB + c], v2 = vpt[(3 * pl + 2) * NB + c];
         const bool own = (c / 3) == cam;
-        st_stream2<2>(reinterpret_cast<double *>(dst + c), (own ? t0[c % 3] : 0.0) - (jp[0] * v0 + jp[1] * v1 + jp[2] * v2),
+        st2(reinterpret_cast<double *>(dst + c), (own ? t0[c % 3] : 0.0) - (jp[0] * v0 + jp[1] * v1 + jp[2] * v2),
                       (own ? t1[c % 3] : 0.0) - (jp[3] * v0 + jp[4] * v1 + jp[5] * v2));
       }
     }
@@ -4402,6 +4282,21 @@ struct Arena {
 
 inline int nblk(long n, int t = TPB) { return (int)std::max<long>(1, (n + t - 1) / t); }  // (never an empty grid: the kernels test their index)
 
+// The environment switches of a solve, read once at the top of ba_solve_impl: mostly cross-checks of the tests; INTEGRATION.md lists the rest.
+struct BaSwitches {
+  bool no_sband = getenv("OSFM_BA_NO_SBAND") != nullptr;            // few shots keep the cyclic reduction, not sband_factor_kernel (test_gpu_ba, test_emu_ba)
+  bool check_band = getenv("OSFM_BA_CHECK_BAND") != nullptr;        // the matrix-core band assembly checked against the per-shot kernel (test_gpu_ba)
+  bool band_per_shot = getenv("OSFM_BA_BAND_PER_SHOT") != nullptr;  // the per-shot band assembly instead of band_mfma_kernel (test_gpu_ba)
+  bool wide_ldlt = getenv("OSFM_BA_WIDE_LDLT") != nullptr;          // the wide band by the block LDL^T chain, not the dense-cluster reduction (test_gpu_ba)
+  const char *dense_cr_budget = getenv("OSFM_BA_DENSE_CR_BUDGET");  // bytes standing in for the free memory the dense clusters need (test_emu_ba)
+  bool gen_full_rows = getenv("OSFM_BA_GEN_FULL_ROWS") != nullptr;  // general BA keeps every row's border slots, not COMPACT rows (test_gpu_bundle_general, test_emu_ba)
+  bool no_fast = getenv("OSFM_BA_NO_FAST") != nullptr;              // no straight-line iteration (test_emu_ba)
+  int fast_fail_at = getenv("OSFM_BA_FAST_FAIL_AT") ? atoi(getenv("OSFM_BA_FAST_FAIL_AT")) : -1;  // its check fails at this LM iteration (test_emu_ba)
+  bool trace = getenv("OSFM_BA_TRACE") != nullptr;                  // a line per phase on stderr, the streams drained: where a solve stalls (test_emu_ba)
+  bool spin = getenv("OSFM_BA_NO_SPIN") == nullptr;                 // a round trip spins on the device's sequence number ...
+  double spin_us = getenv("OSFM_BA_SPIN_US") ? atof(getenv("OSFM_BA_SPIN_US")) : 2000.0;  // ... for this long, then hipStreamSynchronize
+};
+
 struct Solver {
   osfm_ctx *ctx;
   Dev d;
@@ -4413,7 +4308,7 @@ struct Solver {
   double *hscal = nullptr;  // 32 doubles
   int *hstat = nullptr;     // 4 ints
   double *hrr = nullptr;    // the blocks' shares of r.r (nbr doubles)
-  int pinned(int nbr) {
+  int pinned(int nbr, const BaSwitches &sw) {
     const size_t need = (size_t)(32 + 2 + nbr + 8) * sizeof(double);
     if (ctx->h_pinned_bytes < need) {
       if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -4432,8 +4327,8 @@ struct Solver {
     seq = 0;
     // (measured on the local problem: 4.89 -> 4.63 - 4.80 ms of run for ten iterations, 4.24 -> 4.20 ms per LM iteration at configs[4]; OSFM_BA_NO_SPIN
     //  keeps the copy + stream synchronisation)
-    spin = getenv("OSFM_BA_NO_SPIN") == nullptr;
-    if (const char *su = getenv("OSFM_BA_SPIN_US")) spin_us = atof(su);
+    spin = sw.spin;
+    spin_us = sw.spin_us;
     if (spin) OSFM_HIP(hipHostGetDevicePointer(&dev_pinned, ctx->h_pinned, 0));
     return OSFM_OK;
   }
@@ -4466,7 +4361,7 @@ struct Solver {
     }
     return OSFM_OK;
   }
-  double spin_us = 2000.0;
+  double spin_us = 0.0;
 
   void rot(const double *poses) { hipLaunchKernelGGL(shot_rot_kernel, dim3(nblk(d.S, 64)), dim3(64), 0, st, d, poses); }
 
@@ -4474,12 +4369,6 @@ struct Solver {
   int *g_cols = nullptr, *g_col_pos = nullptr;  // generic exact border: the border columns some view holds, and their positions (-1: none)
   int g_ncols = 0;
   double *g_wB = nullptr, *g_vpartB = nullptr;  // rows x ncols x NR, views x ncols x KW
-  // five columns per launch of gen_border_shot_kernel for up to nine border slots (a Brown camera: two launches instead of three; measured 7.46
-  // against 7.96 ms per LM iteration at configs[4] although the kernel then runs one wave per SIMD); OSFM_BA_BORDER_CH3 = three per launch
-  bool gen_border_ch5 = getenv("OSFM_BA_BORDER_CH3") == nullptr;
-  // round 6: all nine columns of a Brown camera in ONE launch (the rows are recomputed once, a record of wB is read once: 5.31 -> 5.16 ms per LM iteration
-  // at configs[4]; OSFM_BA_BORDER_CH5 keeps the two launches of five and four columns)
-  bool gen_border_ch9 = getenv("OSFM_BA_BORDER_CH5") == nullptr;
   int gen_uniform_model = -1;  // every camera has this projection type (the evaluation kernel is specialised for the common ones), -1: mixed
   bool gen_compact = false;    // ... and the rows keep (Xc, wt) instead of their border slots (gen_eval_kernel's COMPACT layout)
   bool have_bpri = false;  // a prior couples an instance with a free border block (position prior with a free bias, up vector / compass with a free rig camera)
@@ -4602,10 +4491,11 @@ struct Solver {
         hipLaunchKernelGGL((gen_border_point_kernel<NRV, MV, (MV >= 0)>), dim3(d.nwg), dim3(kCoopObs), 0, sq, d, (const int *)g_cols, g_ncols, g_wB);
       else
         hipLaunchKernelGGL((gen_border_point_kernel<NRV>), dim3(d.nwg), dim3(kCoopObs), 0, sq, d, (const int *)g_cols, g_ncols, g_wB);
+      // up to nine slots (a Brown camera): more than five columns in ONE launch (round 6: 5.31 -> 5.16 ms per LM iteration at configs[4] against two
+      // launches of five and four), else five per launch (7.46 against 7.96 ms per LM iteration for three per launch at one wave per SIMD)
       if (d.g.KW <= 4) gen_border_chunks<NRV, 4, 4, MV>(sq);
-      else if (d.g.KW <= 9 && g_ncols > 5 && gen_border_ch9) gen_border_chunks<NRV, 9, 9, MV>(sq);
-      else if (d.g.KW <= 9 && gen_border_ch5) gen_border_chunks<NRV, 9, 5, MV>(sq);
-      else if (d.g.KW <= 9) gen_border_chunks<NRV, 9, 3, MV>(sq);
+      else if (d.g.KW <= 9 && g_ncols > 5) gen_border_chunks<NRV, 9, 9, MV>(sq);
+      else if (d.g.KW <= 9) gen_border_chunks<NRV, 9, 5, MV>(sq);
       else if (d.g.KW <= 16) gen_border_chunks<NRV, 16, 2, MV>(sq);
       else gen_border_chunks<NRV, kGenMaxKW, 2, MV>(sq);
     }
@@ -4735,41 +4625,7 @@ struct Solver {
   }
   // A_k <- A_k^-1 for `batch` SPD qm x qm blocks `strideA` apart: blocked Gauss-Jordan, panels of qT columns.  Per panel J:
   //   P = A_JJ^-1 (LDS), R = A_J,: and C = A_:,J copied (C's pivot rows zeroed);  Rn = P R;  A -= C Rn;  A_:,J = -C P;  A_J,: = Rn, A_JJ = P
-  // look-ahead: stream st3 runs the pivot chain (dgj_pivot_ahead_kernel) beside the products of the panel before
-  hipStream_t st3 = nullptr;
-  hipEvent_t ev_rn[2] = {nullptr, nullptr}, ev_p[2] = {nullptr, nullptr};
-  int dbcr_invert_batch_ahead(double *A, long strideA, int batch, int *d_status) {
-    const int m = d.qm, T = d.qT;
-    const double one = 1.0, neg = -1.0, zero = 0.0;
-    const long sP = (long)T * T, sR = (long)T * m;
-    const size_t lds = (size_t)2 * kWB * kWLd * sizeof(double);
-    double *Pb[2] = {d.qP, d.qP2};
-    hipLaunchKernelGGL(dgj_pivot_ahead_kernel, dim3(1, batch), dim3(256), lds, st, A, strideA, m, T, 1, 0, 0, std::min(T, m), (const double *)nullptr,
-                       (const double *)nullptr, (const double *)nullptr, Pb[0], d_status);
-    int J = 0;
-    for (int j0 = 0; j0 < m; j0 += T, J++) {
-      const int w = std::min(T, m - j0), jn = j0 + T, wn = jn < m ? std::min(T, m - jn) : 0;
-      double *P = Pb[J & 1];
-      const int ncopy = (int)std::min<long>(64, ((long)w * m + 255) / 256);
-      hipLaunchKernelGGL(dgj_copy_kernel, dim3(ncopy, batch), dim3(256), 0, st, (const double *)A, strideA, m, T, j0, w, jn, wn, d.qR, d.qC, d.qBn);
-      dgemm_sb(false, false, w, m, w, one, P, T, sP, d.qR, T, sR, zero, d.qRn, T, sR, batch);
-      if (wn > 0) {
-        OSFM_HIP(hipEventRecord(ev_rn[J & 1], st));
-        OSFM_HIP(hipStreamWaitEvent(st3, ev_rn[J & 1], 0));
-        hipLaunchKernelGGL(dgj_pivot_ahead_kernel, dim3(1, batch), dim3(256), lds, st3, (const double *)A, strideA, m, T, 0, w, jn, wn, (const double *)d.qC,
-                           (const double *)d.qRn, (const double *)d.qBn, Pb[(J + 1) & 1], d_status);
-        OSFM_HIP(hipEventRecord(ev_p[(J + 1) & 1], st3));
-      }
-      gemm_launch({gemm_prob(false, false, m, m, w, neg, d.qC, m, sR, d.qRn, T, sR, one, A, m, strideA, batch, j0, j0 + w),
-                   gemm_prob(false, false, m, w, w, neg, d.qC, m, sR, P, T, sP, zero, A + (long)j0 * m, m, strideA, batch)});
-      hipLaunchKernelGGL(dgj_scatter_kernel, dim3((unsigned)(((long)w * m + 255) / 256), batch), dim3(256), 0, st, A, strideA, m, T, j0, w, (const double *)P,
-                         (const double *)d.qRn);
-      if (wn > 0) OSFM_HIP(hipStreamWaitEvent(st, ev_p[(J + 1) & 1], 0));  // before the next panel's copies overwrite what the pivot kernel reads
-    }
-    return OSFM_OK;
-  }
   int dbcr_invert_batch(double *A, long strideA, int batch, int *d_status) {
-    if (st3) return dbcr_invert_batch_ahead(A, strideA, batch, d_status);
     const int m = d.qm, T = d.qT;
     const double one = 1.0, neg = -1.0, zero = 0.0;
     const long sP = (long)T * T, sR = (long)T * m;
@@ -4794,7 +4650,6 @@ struct Solver {
       static OsfmPerDeviceOnce once;
       const int rca = once.run(ctx->device, []() -> int {
         OSFM_HIP(hipFuncSetAttribute((const void *)dgj_pivot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        OSFM_HIP(hipFuncSetAttribute((const void *)dgj_pivot_ahead_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         return OSFM_OK;
       });
       if (rca != OSFM_OK) return rca;
@@ -5206,6 +5061,7 @@ extern "C" int osfm_ba_solve(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_op
 
 static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_options *O, osfm_ba_report *Rp, const GenInput *G) {
   OSFM_REQUIRE(ctx && P && O && Rp, OSFM_E_INVALID, "osfm_ba_solve: null argument");
+  const BaSwitches sw;
   const bool gen = G != nullptr;
   if (gen) {
     OSFM_REQUIRE(P->n_cameras > 0 && P->n_shots > 0 && P->n_points >= 0 && P->n_obs >= 0, OSFM_E_INVALID, "empty bundle problem");
@@ -5252,29 +5108,17 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   sv.ctx = ctx;
   sv.st = ctx->stream;
   A.st = sv.st;
-  struct SideStream {
-    Solver &sv;
-    ~SideStream() {
-      for (int q = 0; q < 2; q++) {
-        if (sv.ev_rn[q]) (void)hipEventDestroy(sv.ev_rn[q]);
-        if (sv.ev_p[q]) (void)hipEventDestroy(sv.ev_p[q]);
-      }
-      if (sv.st3) (void)hipStreamDestroy(sv.st3);
-    }
-  } side_stream{sv};
-  if (getenv("OSFM_BA_ONE_STREAM") == nullptr) {  // measurement knob: everything on one stream
-    // the side stream and its two events live in the context (creating and destroying a stream per solve is a millisecond of a local
-    // bundle adjustment's call); (a low-priority side stream was measured: no difference)
-    // (round 6, measured and dropped: the side stream confined to 192 / 128 / 64 CUs by hipExtStreamCreateWithCUMask so that the cyclic
-    //  reduction's 117 KB workgroups find free LDS elsewhere -- 2.93 - 2.98 ms per LM iteration at configs[4] for every mask, as without one:
-    //  profiles/r06_ba_variants4_side_cu_mask.json)
-    if (!ctx->stream_b) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-    for (int q = 0; q < 2; q++)
-      if (!ctx->ev_side[q]) OSFM_HIP(hipEventCreateWithFlags(&ctx->ev_side[q], hipEventDisableTiming));
-    sv.st2 = ctx->stream_b;
-    sv.ev_fork = ctx->ev_side[0];
-    sv.ev_join = ctx->ev_side[1];
-  }
+  // the side stream and its two events live in the context (creating and destroying a stream per solve is a millisecond of a local
+  // bundle adjustment's call); (a low-priority side stream was measured: no difference)
+  // (round 6, measured and dropped: the side stream confined to 192 / 128 / 64 CUs by hipExtStreamCreateWithCUMask so that the cyclic
+  //  reduction's 117 KB workgroups find free LDS elsewhere -- 2.93 - 2.98 ms per LM iteration at configs[4] for every mask, as without one:
+  //  profiles/r06_ba_variants4_side_cu_mask.json)
+  if (!ctx->stream_b) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
+  for (int q = 0; q < 2; q++)
+    if (!ctx->ev_side[q]) OSFM_HIP(hipEventCreateWithFlags(&ctx->ev_side[q], hipEventDisableTiming));
+  sv.st2 = ctx->stream_b;
+  sv.ev_fork = ctx->ev_side[0];
+  sv.ev_join = ctx->ev_side[1];
   sv.loss = O->loss;
   sv.loss_a = O->loss_threshold;
   Dev &d = sv.d;
@@ -5321,14 +5165,13 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     sv.gen_uniform_model = G->cam_model[0];
     for (int c = 1; c < NC; c++)
       if (G->cam_model[c] != G->cam_model[0]) sv.gen_uniform_model = -1;
-    if (getenv("OSFM_BA_GENERIC_EVAL") != nullptr) sv.gen_uniform_model = -1;  // (self-check knob: the unspecialised evaluation kernel)
     {  // the COMPACT rows: one 2-D projection type, reprojection rows only, no free rig camera (its six columns are border slots too); OSFM_BA_GEN_FULL_ROWS keeps the slots
       bool rc_free = false, depth_rows = false;
       for (int q = 0; q < NRC; q++) rc_free = rc_free || (rc_col[(size_t)q] >= 0 && rc_useful[(size_t)q]);
       if (G->obs_kind)
         for (long o = 0; o < M && !depth_rows; o++) depth_rows = G->obs_kind[o] != 0;
       const int um = sv.gen_uniform_model;
-      sv.gen_compact = !spherical && !rc_free && !depth_rows && getenv("OSFM_BA_GEN_FULL_ROWS") == nullptr &&
+      sv.gen_compact = !spherical && !rc_free && !depth_rows && !sw.gen_full_rows &&
                        (um == OSFM_CAMERA_BROWN || um == OSFM_CAMERA_FISHEYE_OPENCV || um == OSFM_CAMERA_PERSPECTIVE);
     }
     int KW = 0;
@@ -5618,7 +5461,8 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   // (round 6: the dense-cluster solver takes over where the LDS clusters end, at half-width 11 -- until round 5 at 16, and half-widths 11 .. 15 fell to
   //  the sequential band Cholesky WITHOUT the exact border: 180 - 244 CG iterations per LM iteration on a 27-shot scene with nine free cameras)
   constexpr int kLdsBw = 10;  // widest band whose clusters (6 cs unknowns, cs >= bw) the cyclic reduction holds in LDS
-  const bool wide = O->preconditioner == 0 && S >= 2 && bw_true > kLdsBw && bw_true <= kWMaxBw && getenv("OSFM_BA_NO_WIDE") == nullptr;
+  static_assert(kLdsBw <= kSbMaxBw, "the one-workgroup band factor runs on the LDS clusters' bands");
+  const bool wide = O->preconditioner == 0 && S >= 2 && bw_true > kLdsBw && bw_true <= kWMaxBw;
   d.bw = O->preconditioner == 1 ? 0 : (wide ? bw_true : std::min(bw_true, kMaxBw));
   if (S < 2) d.bw = 0;
   // band columns per launch of the per-shot assembly: all of them when one copy fits a workgroup's LDS, else equal slices of at most kBandSlice
@@ -5627,16 +5471,15 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   while (band_copies > 1 && (size_t)band_slice * 36 * band_copies * sizeof(double) > 150 * 1024) band_copies /= 2;
   d.band = A.alloc<double>((size_t)S * (d.bw + 1) * 36, e);
   // exact narrow band, one observation per (track, shot): assembled on the matrix cores (band_mfma_kernel), else per shot with LDS atomics
-  const bool win_band = d.bw >= 1 && d.bw <= kMaxBw && d.bw == bw_true && !track_repeats_shot && bp_pts != nullptr && getenv("OSFM_BA_BAND_PER_SHOT") == nullptr &&
+  const bool win_band = d.bw >= 1 && d.bw <= kMaxBw && d.bw == bw_true && !track_repeats_shot && bp_pts != nullptr && !sw.band_per_shot &&
                         !(gen && g.NRr == 3);  // (it forms E from the two-row layout of the Jacobian copy)
   size_t win_lds = 0;
   int win_grid = 0;
   // the E blocks as an array: the per-shot assembly's operand only (the matrix-core assembly forms them from the Jacobian copy it reads)
-  d.Epm = d.bw > 0 && (!win_band || getenv("OSFM_BA_CHECK_BAND") != nullptr) ? A.alloc<double>((size_t)18 * M, e) : nullptr;
+  d.Epm = d.bw > 0 && (!win_band || sw.check_band) ? A.alloc<double>((size_t)18 * M, e) : nullptr;
   if (win_band) {
     const int TL = d.bw + 1;
     d.bpNT = (6 * TL + 15) / 16;
-    d.bpMode = getenv("OSFM_BA_BM_MODE") ? atoi(getenv("OSFM_BA_BM_MODE")) : 0;
     d.bpPC = kBmSlots / TL;
     d.bpR = (int)std::min<long>(8, std::max<long>(1, ((long)NP + 128L * S - 1) / (128L * S)));
     win_grid = S * d.bpR;
@@ -5657,7 +5500,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   // per-shot assembly with accumulators over the partners a shot really has (band_assemble_compact_kernel): tables once, at setup
   d.bslot = nullptr;
   int bslot_n = 0, bslot_copies = 1;
-  if (d.bw > kMaxBw && !win_band && getenv("OSFM_BA_BAND_FULL_ROWS") == nullptr) {
+  if (d.bw > kMaxBw && !win_band) {
     unsigned char *tab = A.alloc<unsigned char>((size_t)S * (d.bw + 1), e);
     int *d_mx = A.alloc<int>(1, e);
     OSFM_REQUIRE(e == hipSuccess, OSFM_E_NOMEM, "BA device allocation/upload failed: %s", hipGetErrorString(e));
@@ -5675,7 +5518,6 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   d.cs = 0; d.ncl = 0; d.ncd = 0;
   if (d.bw >= 1 && d.bw <= kLdsBw && d.bw == bw_true && O->preconditioner == 0) {  // exact band, dense clusters fit LDS
     d.cs = d.bw < 2 ? 2 : d.bw;
-    if (const char *ecs = getenv("OSFM_BA_CS")) d.cs = std::min(10, std::max(d.cs, atoi(ecs)));  // measurement knob: larger clusters (>= bw)
     d.ncd = 6 * d.cs;
     d.ncl = (S + d.cs - 1) / d.cs;
     const size_t nb = (size_t)d.ncl * d.ncd * d.ncd;
@@ -5693,21 +5535,22 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     d.bHt = A.alloc<double>(nb, e);
     d.bx = A.alloc<double>((size_t)kWalkRhs * d.ncl * d.ncd, e);  // up to kWalkRhs right-hand sides at a time (the camera border's columns + the solve's)
     // few shots: the whole band in one workgroup's LDS (OSFM_BA_NO_SBAND keeps the cyclic reduction: the cross-check of the tests)
-    sv.use_sband = sband_factor_lds(S, d.bw) <= kSbLdsMax && sband_solve_lds(S, d.bw) <= kSbLdsMax && getenv("OSFM_BA_NO_SBAND") == nullptr;
+    sv.use_sband = d.bw <= kSbMaxBw && sband_factor_lds(S, d.bw) <= kSbLdsMax && sband_solve_lds(S, d.bw) <= kSbLdsMax && !sw.no_sband;
     if (sv.use_sband) sv.sbL = A.alloc<double>((size_t)S * (d.bw + 1) * 36, e);
   }
   d.wNB = 0; d.wWb = 0;
   d.qN = 0; d.qm = 0; d.qcs = 0;
   // wide band: cyclic reduction over dense clusters (dbcr_*); OSFM_BA_WIDE_LDLT keeps round 3's block LDL^T chain (measurement knob)
-  bool dense_cr = wide && getenv("OSFM_BA_WIDE_LDLT") == nullptr;
+  bool dense_cr = wide && !sw.wide_ldlt;
   if (dense_cr) {
     // the dense-cluster blocks take ~9 (6 bw)^2 doubles per cluster plus the panel buffers, 2-3 x the LDL^T window's tiles: when the
     // device cannot hold them beside everything already allocated, the block LDL^T chain below (slower, a third of the memory) solves
     // the same band instead of the call failing with OSFM_E_NOMEM.  OSFM_BA_DENSE_CR_BUDGET (bytes) stands in for the free memory in tests.
     const size_t qm = (size_t)6 * d.bw, nq = (size_t)(S + d.bw - 1) / d.bw, np = (qm + kWB - 1) / kWB, qT = ((qm + np - 1) / np + 5) / 6 * 6;
+    // (3 qT^2: two of those pivot tiles belonged to the removed look-ahead variant; kept so that the choice between the two factorisations stays put)
     const size_t need = (nq * qm * qm * 9 + nq * qm * 8 + (nq / 2 + 1) * (3 * qT * qT + 3 * qT * qm)) * sizeof(double);
     size_t free_b = 0, total_b = 0;
-    if (const char *bud = getenv("OSFM_BA_DENSE_CR_BUDGET")) free_b = (size_t)atoll(bud);
+    if (sw.dense_cr_budget) free_b = (size_t)atoll(sw.dense_cr_budget);
     else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = ~(size_t)0;
     else free_b += ctx->pool_bytes;  // the context's cached blocks are not "free" to the runtime, but an allocation that fails takes them back
     if (need > free_b - free_b / 8) dense_cr = false;
@@ -5732,18 +5575,6 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       d.qR = A.alloc<double>(nb * d.qT * d.qm, e);
       d.qRn = A.alloc<double>(nb * d.qT * d.qm, e);
       d.qC = A.alloc<double>(nb * d.qT * d.qm, e);
-      d.qP2 = A.alloc<double>(nb * d.qT * d.qT, e);
-      d.qBn = A.alloc<double>(nb * d.qT * d.qT, e);
-    }
-    // (measured in round 4 and left off: 131.3 against 117.5 ms for ten LM iterations on the 50 x 100 grid, 68.2 against 66.2 ms on ragged
-    // tracks -- two cross-stream hand-overs per panel cost more than the 60 us of pivot inversion they hide, as with round 3's two-stream
-    // LDL^T; OSFM_BA_LOOKAHEAD=1 turns it on, tests/test_gpu_ba.py keeps it correct)
-    if (getenv("OSFM_BA_LOOKAHEAD") != nullptr && getenv("OSFM_BA_ONE_STREAM") == nullptr) {
-      OSFM_HIP(hipStreamCreateWithFlags(&sv.st3, hipStreamNonBlocking));
-      for (int q = 0; q < 2; q++) {
-        OSFM_HIP(hipEventCreateWithFlags(&sv.ev_rn[q], hipEventDisableTiming));
-        OSFM_HIP(hipEventCreateWithFlags(&sv.ev_p[q], hipEventDisableTiming));
-      }
     }
   }
   if (wide && !dense_cr) {
@@ -5784,7 +5615,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       sv.g_vpartB = A.alloc<double>((size_t)std::max(1, G->NV) * std::max(1, sv.g_ncols) * std::max(1, g.KW), e);
     }
   }
-  bool border_ok = getenv("OSFM_BA_NO_BORDER") == nullptr;  // exact camera border: every camera free (generic mode: the border holds free blocks only)
+  bool border_ok = true;  // exact camera border: every camera free (generic mode: the border holds free blocks only)
   bool all_cams_fixed = !gen;
   for (int c = 0; c < NC && !gen; c++) {
     if (P->cam_fixed[c]) border_ok = false;
@@ -5801,7 +5632,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   const int nred = d.nred;
   const int nbr = nblk(nred);
   {
-    const int rcp = sv.pinned(nbr);
+    const int rcp = sv.pinned(nbr, sw);
     if (rcp != OSFM_OK) return rcp;
   }
   double *hs = sv.hscal;
@@ -5810,33 +5641,16 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   double cost = 0, sumsq = 0;
   int rc = sv.eval(d.cams, d.poses, d.pts, true, &cost, &sumsq);
   if (rc != OSFM_OK) return rc;
-  if (getenv("OSFM_BA_DEBUG_NAN") != nullptr) {  // debugging aid: which of the first evaluation's arrays hold a NaN
-    OSFM_HIP(hipStreamSynchronize(st));
-    auto scan = [&](const char *name, const double *p, size_t n) {
-      std::vector<double> h(n);
-      (void)hipMemcpy(h.data(), p, n * sizeof(double), hipMemcpyDeviceToHost);
-      size_t bad = 0;
-      for (double x : h) bad += !(x == x);
-      if (bad) fprintf(stderr, "[osfm_ba] %s: %zu of %zu not finite\n", name, bad, n);
-    };
-    scan("Jpm", d.Jpm, (size_t)(gen ? g.ncomp : kRowComps) * M);
-    scan("sm_wt", d.sm_wt, (size_t)M);
-    if (gen) {
-      scan("PI", g.PI, (size_t)36 * S);
-      scan("gpri", g.gpri, (size_t)nred);
-    }
-  }
   Rp->initial_cost = cost;
   Rp->seconds_setup = std::chrono::duration<double>(t_run - t_start).count();
   Rp->rmse_normalized_initial = std::sqrt(sumsq / (double)std::max<long>(1, gen ? G_rows0 : M));
   Rp->cost_history[0] = cost;
-  const bool trace = getenv("OSFM_BA_TRACE") != nullptr;  // debugging aid: a line per phase with the stream drained, to see where a solve stalls
   auto mark = [&](const char *what) -> int {
-    if (!trace) return OSFM_OK;
+    if (!sw.trace) return OSFM_OK;
     fprintf(stderr, "[osfm_ba trace] %s ...", what);
     fflush(stderr);
     OSFM_HIP(hipStreamSynchronize(st));
-    if (sv.st2) OSFM_HIP(hipStreamSynchronize(sv.st2));
+    OSFM_HIP(hipStreamSynchronize(sv.st2));
     OSFM_HIP(hipGetLastError());
     fprintf(stderr, " done\n");
     return OSFM_OK;
@@ -5845,8 +5659,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   double radius = O->initial_radius > 0 ? O->initial_radius : 1e4;
   double decrease_factor = 2.0;
   bool need_prepare = true, have_scale = false;
-  bool fast_ok = getenv("OSFM_BA_NO_FAST") == nullptr;  // the straight-line iteration is tried (until it fails once in this solve)
-  const int fast_fail_at = getenv("OSFM_BA_FAST_FAIL_AT") ? atoi(getenv("OSFM_BA_FAST_FAIL_AT")) : -1;
+  bool fast_ok = !sw.no_fast;  // the straight-line iteration is tried (until it fails once in this solve)
   int n_invalid = 0, iter = 0;
   double gmax = 0;
   Rp->termination = 0;
@@ -5896,8 +5709,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     const bool want_border = d.bw > 0 && (d.ncl > 0 || wide) && O->preconditioner == 0 && sv.Bc && border_ok;
     // few shots, constant cameras: the one-workgroup factorisation carries the solve, so the right-hand side goes in front of it, on the main stream -- the
     // side stream has nothing to do in such an iteration (side2 = null)
-    const bool sband_fuse = sv.use_sband && !gen && all_cams_fixed && d.bw > 0 && d.ncl > 0 && O->preconditioner == 0 && !want_border &&
-                            getenv("OSFM_BA_NO_SBAND_FUSE") == nullptr;
+    const bool sband_fuse = sv.use_sband && !gen && all_cams_fixed && d.bw > 0 && d.ncl > 0 && O->preconditioner == 0 && !want_border;
     hipStream_t side2 = sband_fuse ? nullptr : sv.st2;
     hipStream_t sx = side2 ? side2 : st;
     // where the side stream starts: the per-shot assembly (LDS atomics) leaves HBM idle, so the border's passes run beside it; the
@@ -5915,7 +5727,6 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
                          (double *)nullptr);
       fork_at = 0;
     }
-    if (const char *fk = getenv("OSFM_BA_FORK")) fork_at = std::min(2, std::max(0, fk[0] - '0'));
     const bool fork_late = fork_at >= 1;
     if (side2 && !fork_late) {
       OSFM_HIP(hipEventRecord(sv.ev_fork, st));
@@ -5950,7 +5761,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
           default: hipLaunchKernelGGL(band_mfma_kernel<6>, dim3(win_grid), dim3(384), win_lds, st, d); break;
         }
         hipLaunchKernelGGL(band_finish_kernel, dim3(nblk((long)S * (d.bw + 1) * 36)), dim3(TPB), 0, st, d, radius);
-        if (getenv("OSFM_BA_CHECK_BAND") != nullptr) {  // self-check knob of the tests: the per-shot kernel must agree to rounding
+        if (sw.check_band) {  // self-check knob of the tests: the per-shot kernel must agree to rounding
           const size_t nbd = (size_t)S * (d.bw + 1) * 36;
           std::vector<double> b_win(nbd), b_shot(nbd);
           OSFM_HIP(hipMemcpyAsync(b_win.data(), d.band, nbd * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -5993,14 +5804,8 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
         OSFM_HIP(hipEventRecord(sv.ev_fork, st));
         OSFM_HIP(hipStreamWaitEvent(side2, sv.ev_fork, 0));
       }
-      if (want_border && gen && getenv("OSFM_BA_BORDER_BY_MATVECS") == nullptr) {
+      if (want_border && gen) {
         sv.gen_border_columns(radius, sx);
-      } else if (want_border && gen) {  // (self-check knob) column j = the mat-vec of the unit vector e_(cam0 + j): its instance rows are B's, its border rows C's
-        for (int j = 0; j < nbord; j++) {
-          hipLaunchKernelGGL(unit_vec_kernel, dim3(nbr), dim3(TPB), 0, sx, d.p, nred, d.cam0 + j);
-          sv.gen_matvec(d.p, d.Ap, radius, sx);
-          hipLaunchKernelGGL(gen_border_store_kernel, dim3(nbr), dim3(TPB), 0, sx, (const double *)d.Ap, sv.Bc, sv.dCm, j, nbord, 6 * S);
-        }
       } else if (want_border) {  // all nb columns of B (and of the camera block C) in one pass over the observations
         if (3 * NC == 3) {
           hipLaunchKernelGGL(border_point_kernel<3>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, sv.wB);
@@ -6300,7 +6105,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     // path.  Three round trips per LM iteration become one (OSFM_BA_NO_FAST keeps the careful path: the cross-check of the tests).
     bool fast_done = false;
     const bool exact_expected = (try_bcr || wide) && (try_border || (gen ? g.NB == 0 : all_cams_fixed)) && O->pcg_direct_tolerance > O->pcg_tolerance;
-    if (exact_expected && fast_ok && !trace) {
+    if (exact_expected && fast_ok && !sw.trace) {
       start_pcg_enqueue();
       pcg_half(0, true);
       rc = candidate_enqueue(true);
@@ -6314,7 +6119,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       for (int q = 0; q < nbr; q++) rr += rr_part[(size_t)q];
       const bool status_ok = !((try_bcr && hst[0] != 0) || (sv.use_wide && hst[2] != 0) || (sv.use_border && hst[1] != 0));
       const double tol_first = std::max(O->pcg_tolerance, O->pcg_direct_tolerance);
-      const bool forced_failure = fast_fail_at == iter;  // test knob OSFM_BA_FAST_FAIL_AT: the way back to the careful path, exercised on purpose
+      const bool forced_failure = sw.fast_fail_at == iter;  // test knob OSFM_BA_FAST_FAIL_AT: the way back to the careful path, exercised on purpose
       if (!forced_failure && status_ok && bb1 == bb1 && !std::isinf(bb1) && bb1 > 0 && rr == rr && rr <= tol_first * tol_first * bb1) {
         k = 1;
         Rp->pcg_iterations_total += 1;
@@ -6382,7 +6187,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       Rp->pcg_iterations_total += k;
     }
     if (mark("pcg") != OSFM_OK) return OSFM_E_HIP;
-    if (trace) fprintf(stderr, "[osfm_ba trace] iteration %d: %d pcg iterations, status %d %d %d, band %d bcr %d (one workgroup: %d) wide %d dense %d border %d\n", iter, k, hst[0], hst[1],
+    if (sw.trace) fprintf(stderr, "[osfm_ba trace] iteration %d: %d pcg iterations, status %d %d %d, band %d bcr %d (one workgroup: %d) wide %d dense %d border %d\n", iter, k, hst[0], hst[1],
                        hst[2], (int)sv.use_band, (int)sv.use_bcr, (int)(sv.use_bcr && sv.use_sband), (int)sv.use_wide, (int)(sv.use_wide && dense_cr), (int)sv.use_border);
     rc = candidate_enqueue();
     if (rc != OSFM_OK) return rc;

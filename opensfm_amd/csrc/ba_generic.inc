@@ -1431,12 +1431,6 @@ __global__ void gen_border_rhs_kernel(const double *Bc, const double *SigInv, co
     z[cam0 + threadIdx.x] = acc;
   }
 }
-// column j of the reduced matrix, from a mat-vec with the unit vector e_(cam0 + j): Bc[j] = its instance rows, Cm[:, j] = its border rows
-__global__ void gen_border_store_kernel(const double *col, double *Bc, double *Cm, int j, int nb, int n6) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n6) Bc[(long)j * n6 + t] = col[t];
-  else if (t < n6 + nb) Cm[(t - n6) * nb + j] = col[t];
-}
 
 // ---- exact border, every column that touches observations in ONE pass over them (the generic twin of border_point / border_shot) -----
 // Column c of the reduced matrix = the mat-vec of a unit vector on border unknown c.  A unit vector has no instance part and reaches an

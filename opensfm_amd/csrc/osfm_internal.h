@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdio>
 #include <mutex>
 #include <unordered_map>
 #include <string>
@@ -16,6 +17,20 @@ void osfm_set_error(const char *fmt, ...);
 // kernels of the failed call, so its release waits for the device before the block goes back to the cache (OsfmPoolBuf::release)
 extern thread_local unsigned osfm_error_epoch;
 struct osfm_ctx;
+// OSFM_POOL_BYTES: a plain decimal number of bytes into *out; false (and *out untouched) for anything else -- empty, a sign, a suffix such
+// as "2G" or "2e9", a value past SIZE_MAX
+inline bool osfm_parse_pool_bytes(const char *s, size_t *out) {
+  if (!s || !*s) return false;
+  size_t v = 0;
+  for (; *s; s++) {
+    if (*s < '0' || *s > '9') return false;
+    const size_t digit = (size_t)(*s - '0');
+    if (v > (SIZE_MAX - digit) / 10) return false;
+    v = v * 10 + digit;
+  }
+  *out = v;
+  return true;
+}
 // hipMalloc for the allocations that do not come from the context's block cache: when the device is out of memory while blocks sit
 // idle in the cache, the cache is dropped (osfm_ctx_trim_pool) and the allocation retried
 hipError_t osfm_malloc_retry(osfm_ctx *ctx, void **p, size_t bytes);
@@ -66,7 +81,10 @@ struct osfm_ctx {
   size_t pool_limit = pool_limit_from_env();
   static size_t pool_limit_from_env() {
     const char *e = getenv("OSFM_POOL_BYTES");
-    return e ? (size_t)strtoull(e, nullptr, 10) : kPoolBytes;
+    size_t v = kPoolBytes;
+    if (e && !osfm_parse_pool_bytes(e, &v))
+      fprintf(stderr, "osfm: OSFM_POOL_BYTES=\"%s\" is not a decimal number of bytes; the default %zu is used\n", e, kPoolBytes);
+    return v;
   }
   hipStream_t stream_b = nullptr;  // second stream of the batched matching calls (gather + D2H of chunk k under the matcher of k + 1)
   size_t match_hint = 0;        // int32 entries of the last batched call's match list: the next call reserves that much up front

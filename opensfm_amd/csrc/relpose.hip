@@ -175,9 +175,8 @@ __global__ __launch_bounds__(256, 4) void rp_pose_kernel(Rounds R, int count5, i
 }
 
 // After the rounds: the inlier mask of the RANSAC (mode 0) or the refinement stage of robust_match_calibrated (mode 1), results out
-template <int WPE>
-__global__ __launch_bounds__(kWave, WPE) void rp_finish_kernel(Rounds R, int mode, double threshold_angle, int refine_iterations, int *sub_ws,
-                                                          uint8_t *mask, PairOut *out) {
+__global__ __launch_bounds__(kWave, 2) void rp_finish_kernel(Rounds R, int mode, double threshold_angle, int refine_iterations, int *sub_ws,
+                                                        uint8_t *mask, PairOut *out) {
   __shared__ RefineShared sh;
   const int p = (int)blockIdx.x;
   if (p >= R.n_pairs) return;
@@ -407,13 +406,8 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
     OSFM_HIP(hipGetLastError());
     OSFM_REQUIRE(rounds < 100000, OSFM_E_NUMERIC, "osfm_relpose_pairs: the rounds do not terminate");
   }
-  static const int finish_wpe = getenv("OSFM_RP_FINISH_WPE") ? atoi(getenv("OSFM_RP_FINISH_WPE")) : 2;
-  if (finish_wpe == 2)
-    hipLaunchKernelGGL(rp_finish_kernel<2>, dim3(n_pairs), dim3(kWave), 0, st, R, mode, prm->threshold, (int)prm->refine_iterations, d_sub.as<int>(), d_mask,
-                       (PairOut *)d_out);
-  else
-    hipLaunchKernelGGL(rp_finish_kernel<1>, dim3(n_pairs), dim3(kWave), 0, st, R, mode, prm->threshold, (int)prm->refine_iterations, d_sub.as<int>(), d_mask,
-                       (PairOut *)d_out);
+  hipLaunchKernelGGL(rp_finish_kernel, dim3(n_pairs), dim3(kWave), 0, st, R, mode, prm->threshold, (int)prm->refine_iterations, d_sub.as<int>(), d_mask,
+                     (PairOut *)d_out);
   OSFM_HIP(hipGetLastError());
   OSFM_HIP(hipStreamSynchronize(st));  // the work buffers above are released on return
   if (rounds_out) *rounds_out = rounds;

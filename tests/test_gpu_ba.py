@@ -509,22 +509,6 @@ def test_half_width_beyond_one_assembly_pass(gpu_ctx):
     assert np.allclose(a["cost_history"], b["cost_history"], rtol=1e-6)
 
 
-def test_lookahead_variant_of_the_wide_band_inversion(gpu_ctx, monkeypatch):
-    """OSFM_BA_LOOKAHEAD=1: the pivot chain of the blocked Gauss-Jordan on a second stream (the next panel's pivot block formed and inverted
-    beside the trailing product of the current one) -- measured slower than the single-stream order and off by default, kept correct here:
-    same CG counts give or take a step, same trajectory."""
-    from opensfm_amd import bundle
-
-    pr = synthetic.make_ba_scene_grid(12, 30, 6000, 9, seed=4)
-    a = bundle.bundle_arrays(pr, {"bundle_max_iterations": 5}, **NO_TOL)
-    monkeypatch.setenv("OSFM_BA_LOOKAHEAD", "1")
-    b = bundle.bundle_arrays(pr, {"bundle_max_iterations": 5}, **NO_TOL)
-    monkeypatch.delenv("OSFM_BA_LOOKAHEAD")
-    assert a["preconditioner_bandwidth"] == b["preconditioner_bandwidth"] > 15
-    assert abs(a["pcg_iterations"] - b["pcg_iterations"]) <= 2
-    assert np.allclose(a["cost_history"], b["cost_history"], rtol=1e-10)
-
-
 def test_results_do_not_depend_on_what_the_cached_slabs_held(gpu_ctx):
     """the solve's device arrays are sub-allocated from slabs the context keeps between calls (round 5): whatever a solve reads it must
     have written in the same call.  Two different problems alternate on one context -- each run is bit for bit the run on a fresh

@@ -1,6 +1,5 @@
-// Microbenchmark of the cyclic-reduction level kernel: duration against the number of workgroups, with parts of the kernel switched off
-// (bit 1: no Gauss-Jordan, 2: no output stores, 4: no neighbour products, 8: no global loads), and of one solve walk.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DOSFM_BCR_UBENCH -I opensfm_amd/csrc -I include tools/ubench_bcr.hip \
+// Microbenchmark of the cyclic-reduction level kernel: duration against the number of workgroups, and of one solve walk.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I opensfm_amd/csrc -I include tools/ubench_bcr.hip \
 //         -o tools/ubench_bcr -L opensfm_amd/csrc -losfm_mi355 -Wl,-rpath,'$ORIGIN/../opensfm_amd/csrc'
 #include "ba.hip"
 
@@ -40,30 +39,24 @@ int main() {
     hipMemcpy(d.bE, hE.data(), nb * sizeof(double), hipMemcpyHostToDevice);
     hipMemset(d.bD2, 0, nb * sizeof(double));
   };
-  const int variants[] = {0, 8, 4, 2, 6, 14, 1, 15};
-  for (int v : variants) {
-    hipMemcpyToSymbol(HIP_SYMBOL(osfm_bcr_variant), &v, sizeof(int));
-    printf("variant %2d:", v);
-    for (int wgs : {1, 8, 18, 35, 70, 139, 278}) {
-      reset();
-      hipDeviceSynchronize();
-      float best = 1e9f;
-      for (int rep = 0; rep < 3; rep++) {
-        hipEventRecord(e0, 0);
-        hipLaunchKernelGGL(lv.fn, dim3(wgs), dim3(lv.threads), lv.lds_bytes, 0, d, 1, 0, status);
-        hipEventRecord(e1, 0);
-        hipEventSynchronize(e1);
-        float ms;
-        hipEventElapsedTime(&ms, e0, e1);
-        best = std::min(best, ms);
-      }
-      printf("  %3d wg %7.1f us", wgs, best * 1e3f);
+  printf("level:");
+  for (int wgs : {1, 8, 18, 35, 70, 139, 278}) {
+    reset();
+    hipDeviceSynchronize();
+    float best = 1e9f;
+    for (int rep = 0; rep < 3; rep++) {
+      hipEventRecord(e0, 0);
+      hipLaunchKernelGGL(lv.fn, dim3(wgs), dim3(lv.threads), lv.lds_bytes, 0, d, 1, 0, status);
+      hipEventRecord(e1, 0);
+      hipEventSynchronize(e1);
+      float ms;
+      hipEventElapsedTime(&ms, e0, e1);
+      best = std::min(best, ms);
     }
-    printf("\n");
+    printf("  %3d wg %7.1f us", wgs, best * 1e3f);
   }
+  printf("\n");
   // the whole factorisation and one solve walk, as the solver issues them
-  int v0 = 0;
-  hipMemcpyToSymbol(HIP_SYMBOL(osfm_bcr_variant), &v0, sizeof(int));
   Solver sv;
   sv.d = d;
   sv.st = 0;
