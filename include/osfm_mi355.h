@@ -433,6 +433,52 @@ int osfm_relpose_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const 
                        const osfm_relpose_params *params, int mode, osfm_relpose_result *results, uint8_t *mask,
                        double *kernel_ms /* may be NULL: HIP-event time of the kernels */);
 
+/* =====================================================================================
+ * Rotation-only LO-RANSAC of image pairs (reconstruction.compute_image_pairs): the ranking of candidate initial
+ * pairs of `opensfm reconstruct`.  relrot.hip / relrot_core.h: one wavefront per pair (lane 0 draws the next block of samples,
+ * one 3-point model per lane, the wavefront scores each model over the pair's correspondences in the reference's order); the
+ * same launch computes the rotation-only inlier count and the reconstructability score.  The per-pair walk is pinned bit for
+ * bit by a host build of the same header (tests/test_relrot_host.py) against a sequential restatement on std::mt19937 and
+ * against the reference's robust_estimator.h; the GPU is pinned against that host build (tests/test_gpu_relrot.py).
+ *
+ * osfm_relrot_pairs   pyrobust.ransac_relative_rotation(b1, b2, threshold, params, RANSAC) for every pair of a batch
+ *   (robust/src/instanciations.cc:50-64 -> Estimate<RansacScoring, RelativeRotation>, robust_estimator.h:37-119): pair p owns
+ *   the correspondences offsets[p] .. offsets[p+1]-1 of b1 / b2 (total x 3, first / second of the samples, used as given).
+ *   Sampler std::mt19937(42) with libstdc++'s uniform_int_distribution, ties keep the newcomer, LO on every new or tied best
+ *   with >= 3 inliers (sample size max(min(12, inliers / 2), 3)), ShouldStop with exponent 3 -- as osfm_relpose_pairs.
+ *   result.model / lo_model: ScoreInfo::model / lo_model (3 x 3 row-major; multiview.relative_pose_ransac_rotation_only returns
+ *   lo_model^T); score; iterations run.  mask (total bytes, may be NULL): the inliers of the best score.
+ *   params.inlier_chord > 0: also _two_view_rotation_inliers(b1, b2, lo_model^T, chord) (reconstruction.py:377-384,
+ *   |lo_model^T b2 - b1| < chord) -> n_rotation_inliers, and pairwise_reconstructability(n, n_rotation_inliers)
+ *   (reconstruction.py:193-200) -> reconstructability; inlier_chord <= 0: n_rotation_inliers = -1, reconstructability = 0.
+ *   n_pairs == 0 returns OSFM_OK and touches nothing.  A pair with fewer than 3 correspondences (zero-length included) is
+ *   OSFM_E_INVALID: the reference's sampler never returns there (it cannot draw 3 distinct indices).
+ * osfm_relrot_pairs_pixels   the same from normalised image coordinates p1 / p2 (total x 2): the bearings are computed on the
+ *   device (camera.pixel_bearing_many, as osfm_pixel_bearings) with the cameras pair_cams[2p], pair_cams[2p+1] of the table
+ *   cam_model[n_cams] (OSFM_CAMERA_*) / cam_params[n_cams x 16] (native parameter order, as osfm_match_pairs_calibrated).
+ *   kernel_ms then includes the bearings.
+ * ===================================================================================== */
+typedef struct osfm_relrot_params {
+  double threshold;                /* radians: 4 * config five_point_algo_threshold in compute_image_pairs (0.016) */
+  double probability;              /* RobustEstimatorParams::probability (0.99: relative_pose_ransac_rotation_only never sets it) */
+  double inlier_chord;             /* chord of the rotation-only inlier count (compute_image_pairs: the threshold); <= 0: skipped */
+  int32_t iterations;              /* 1000 (reconstruction.py:409) */
+  int32_t use_lo;                  /* RobustEstimatorParams::use_local_optimization (1) */
+  int32_t lo_iterations;           /* ::local_optimization_iterations (10) */
+  int32_t use_iteration_reduction; /* ::use_iteration_reduction (1) */
+} osfm_relrot_params;
+typedef struct osfm_relrot_result {
+  double model[9], lo_model[9];        /* ScoreInfo::model / lo_model, row-major */
+  int32_t score, iterations;           /* best inlier count, iterations run */
+  int32_t n_rotation_inliers;          /* |lo_model^T b2 - b1| < inlier_chord; -1 when skipped */
+  int32_t reconstructability;          /* pairwise_reconstructability(n, n_rotation_inliers); 0 when skipped */
+} osfm_relrot_result;
+int osfm_relrot_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const int64_t *offsets, int n_pairs, const osfm_relrot_params *params,
+                      osfm_relrot_result *results, uint8_t *mask_or_null, double *kernel_ms /* may be NULL: HIP-event time */);
+int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, const int64_t *offsets, int n_pairs, const int32_t *pair_cams,
+                             const int32_t *cam_model, const double *cam_params, int n_cams, const osfm_relrot_params *params,
+                             osfm_relrot_result *results, uint8_t *mask_or_null, double *kernel_ms /* may be NULL */);
+
 /*
  * Batched pair matching for the pairs that take the calibrated branch of robust_match (opensfm/matching.py:906-929: every pair with
  * a camera that is not an undistorted perspective / brown one): per pair matching.match (matching.py:563-634) = descriptor stage,

@@ -54,6 +54,29 @@ class RelposeParams(C.Structure):
     ]
 
 
+class RelrotParams(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("probability", C.c_double),
+        ("inlier_chord", C.c_double),
+        ("iterations", C.c_int32),
+        ("use_lo", C.c_int32),
+        ("lo_iterations", C.c_int32),
+        ("use_iteration_reduction", C.c_int32),
+    ]
+
+
+class RelrotResult(C.Structure):
+    _fields_ = [
+        ("model", C.c_double * 9),
+        ("lo_model", C.c_double * 9),
+        ("score", C.c_int32),
+        ("iterations", C.c_int32),
+        ("n_rotation_inliers", C.c_int32),
+        ("reconstructability", C.c_int32),
+    ]
+
+
 class RelposeResult(C.Structure):
     _fields_ = [
         ("model", C.c_double * 12),
@@ -132,6 +155,16 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(RelposeParams), C.c_int,
          C.POINTER(RelposeResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_relrot_pairs": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(RelrotParams),
+         C.POINTER(RelrotResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_relrot_pairs_pixels": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(C.c_double), C.c_int, C.POINTER(RelrotParams), C.POINTER(RelrotResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
     ),
     "osfm_match_guided": (
         C.c_int,

@@ -34,6 +34,16 @@ inline bool osfm_parse_pool_bytes(const char *s, size_t *out) {
 // hipMalloc for the allocations that do not come from the context's block cache: when the device is out of memory while blocks sit
 // idle in the cache, the cache is dropped (osfm_ctx_trim_pool) and the allocation retried
 hipError_t osfm_malloc_retry(osfm_ctx *ctx, void **p, size_t bytes);
+namespace osfm_rp {
+struct RngTable;
+}
+// relpose.hip, shared by the LO-RANSAC drivers (relpose.hip, relrot.hip); the caller holds the context lock.
+// The context's device copy of the std::mt19937(42) stream, made on first use:
+int osfm_rng_table(osfm_ctx *ctx, osfm_rp::RngTable *out);
+// ShouldStop's bound (robust_estimator.h:20-35, exponent minimal_samples) for every best inlier count 0 .. n of every pair: *stop holds one
+// table per distinct pair size, pair p's at *stop + (*stop_off)[p]; the tables are cached on the context
+void osfm_stop_tables(osfm_ctx *ctx, const int64_t *offsets, int n_pairs, double probability, int minimal_samples, std::vector<double> *stop,
+                      std::vector<int64_t> *stop_off);
 
 #define OSFM_HIP(call)                                                                      \
   do {                                                                                      \
@@ -90,8 +100,10 @@ struct osfm_ctx {
   size_t match_hint = 0;        // int32 entries of the last batched call's match list: the next call reserves that much up front
   // relpose.hip: ShouldStop's iteration bound for every (pair size n, best inlier count c <= n), tabulated with the host's libm (pow, log);
   // kept between calls -- the pair sizes of a data set repeat, and a cold table for ~300 sizes is ~5 ms of libm calls
+  // (relrot.hip too: the key is (MINIMAL_SAMPLES << 32) | n; osfm_stop_tables bounds the cache by its size in doubles)
   double stop_probability = -1.0;
-  std::unordered_map<int, std::vector<double>> stop_tables;
+  std::unordered_map<long long, std::vector<double>> stop_tables;
+  size_t stop_table_doubles = 0;
   void *h_pinned = nullptr;     // ba.hip: pinned host memory the LM loop's scalars come back through, made on first use
   hipEvent_t ev_side[2] = {nullptr, nullptr};  // ba.hip: fork / join of the solver's side stream (= stream_b), made on first use
   hipStream_t stream_c = nullptr;              // relpose.hip: side stream of the LO-RANSAC rounds, with its fork / join events; made on first use

@@ -20,81 +20,12 @@
 #include <vector>
 
 #include "osfm_internal.h"
+#include "gpu_wave.h"
 #include "relpose_rounds.h"
 
 using namespace osfm_rp;
 
 namespace {
-
-struct GpuWave {  // one wavefront = one workgroup
-  int lane;
-  template <class F>
-  __device__ void single(F f) {
-    __syncthreads();
-    if (lane == 0) f();
-    __syncthreads();
-  }
-  template <class F>
-  __device__ void parallel_for(int n, F f) {
-    __syncthreads();
-    for (int i = lane; i < n; i += kWave) f(i);
-    __syncthreads();
-  }
-  template <class P>
-  __device__ int count_if(int n, P p) {
-    int c = 0;
-    for (int base = 0; base < n; base += kWave) {
-      const int i = base + lane;
-      const bool b = i < n && p(i);
-      c += __popcll(__ballot(b));
-    }
-    return c;
-  }
-  template <class P>
-  __device__ int compact(int n, P p, int *out) {  // ascending indices, as a sequential scan would write them
-    int c = 0;
-    for (int base = 0; base < n; base += kWave) {
-      const int i = base + lane;
-      const bool b = i < n && p(i);
-      const unsigned long long m = __ballot(b);
-      if (b) out[c + __popcll(m & ((1ull << lane) - 1ull))] = i;
-      c += __popcll(m);
-    }
-    __syncthreads();
-    return c;
-  }
-  template <class P>
-  __device__ int compact_changed(int n, P p, int *out, int *changed) {  // compact + "did any entry change"
-    int c = 0;
-    bool diff = false;
-    for (int base = 0; base < n; base += kWave) {
-      const int i = base + lane;
-      const bool b = i < n && p(i);
-      const unsigned long long m = __ballot(b);
-      if (b) {
-        const int k = c + __popcll(m & ((1ull << lane) - 1ull));
-        diff |= out[k] != i;
-        out[k] = i;
-      }
-      c += __popcll(m);
-    }
-    if (__ballot(diff)) *changed = 1;
-    __syncthreads();
-    return c;
-  }
-  __device__ int atomic_add(int *p, int v) { return atomicAdd(p, v); }
-  // a window of the generator stream next to the wavefront: the draws of lane 0 then cost an LDS read each, not a trip to L2
-  __device__ RngView stage_rng(const RngTable &T, uint32_t *buf, int pos, bool want) {
-    int n = 0;
-    if (want) {
-      n = T.size - pos < kRngCache ? T.size - pos : kRngCache;
-      if (n < 0) n = 0;
-      for (int i = lane; i < n; i += kWave) buf[i] = T.tab[pos + i];
-    }
-    __syncthreads();
-    return RngView{T, buf, pos, n};
-  }
-};
 
 struct PairOut {  // mirrors osfm_relpose_result
   double model[12], lo_model[12], R[9], t[3];
@@ -231,18 +162,6 @@ __global__ void pixel_bearings_kernel(int model, CameraParams cam, const double 
   out[3 * i + 2] = b[2];
 }
 
-struct DevBuf {  // frees on scope exit
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-  template <class T>
-  T *as() const {
-    return (T *)p;
-  }
-};
-
 struct Sub {  // a slice of a DevBuf
   void *p;
   template <class T>
@@ -284,6 +203,47 @@ int ensure_relpose_attributes(int device) {
 
 }  // namespace
 
+// the context's device copy of the std::mt19937(42) stream, for the other LO-RANSAC drivers (relrot.hip)
+int osfm_rng_table(osfm_ctx *ctx, RngTable *out) { return rng_table(ctx, out); }
+
+void osfm_stop_tables(osfm_ctx *ctx, const int64_t *offsets, int n_pairs, double probability, int minimal_samples, std::vector<double> *stop,
+                      std::vector<int64_t> *stop_off) {
+  constexpr size_t kCacheDoubles = (size_t)1 << 23;  // 64 MiB of cached tables at most; a larger table is made for its call only
+  if (ctx->stop_probability != probability) {        // the context's tables are for one probability
+    ctx->stop_tables.clear();
+    ctx->stop_table_doubles = 0;
+    ctx->stop_probability = probability;
+  }
+  std::unordered_map<int, int64_t> table_of_n;
+  stop->clear();
+  stop_off->assign((size_t)n_pairs, 0);
+  for (int p = 0; p < n_pairs; p++) {
+    const int n = (int)(offsets[p + 1] - offsets[p]);
+    auto it = table_of_n.find(n);
+    if (it == table_of_n.end()) {
+      it = table_of_n.emplace(n, (int64_t)stop->size()).first;
+      const long long key = ((long long)minimal_samples << 32) | (unsigned)n;
+      auto ct = ctx->stop_tables.find(key);
+      if (ct != ctx->stop_tables.end()) {
+        stop->insert(stop->end(), ct->second.begin(), ct->second.end());
+      } else {
+        std::vector<double> t((size_t)n + 1);
+        for (int c = 0; c <= n; c++) t[(size_t)c] = max_iterations_for(c, n > 0 ? n : 1, probability, minimal_samples);
+        stop->insert(stop->end(), t.begin(), t.end());
+        if (t.size() <= kCacheDoubles / 2) {
+          if (ctx->stop_table_doubles + t.size() > kCacheDoubles || ctx->stop_tables.size() >= 65536) {
+            ctx->stop_tables.clear();
+            ctx->stop_table_doubles = 0;
+          }
+          ctx->stop_table_doubles += t.size();
+          ctx->stop_tables.emplace(key, std::move(t));
+        }
+      }
+    }
+    (*stop_off)[(size_t)p] = it->second;
+  }
+}
+
 // The rounds over device-resident bearings: d_b1 / d_b2 (total x 3), d_off (n_pairs + 1), host copy `offsets`.  Fills d_mask (total) and
 // d_out (n_pairs results).  Everything is enqueued on `st`; the host waits once per round for three counters.
 int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *d_b2, const int64_t *d_off, const int64_t *offsets,
@@ -301,32 +261,10 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
     if (rc != OSFM_OK) return rc;
   }
   // ShouldStop's bound for every possible best inlier count, with the host libm (see relpose_core.h): one table per distinct pair
-  // size n, shared by all pairs of that size (n + 1 pow / log evaluations each)
+  // size n, shared by all pairs of that size (n + 1 pow / log evaluations each), cached on the context
   std::vector<double> stop;
-  std::vector<int64_t> stop_off((size_t)n_pairs);
-  {
-    if (ctx->stop_probability != prm->probability) {  // the context's tables are for one probability
-      ctx->stop_tables.clear();
-      ctx->stop_probability = prm->probability;
-    }
-    if (ctx->stop_tables.size() > 65536) ctx->stop_tables.clear();
-    std::unordered_map<int, int64_t> table_of_n;
-    for (int p = 0; p < n_pairs; p++) {
-      const int n = (int)(offsets[p + 1] - offsets[p]);
-      auto it = table_of_n.find(n);
-      if (it == table_of_n.end()) {
-        it = table_of_n.emplace(n, (int64_t)stop.size()).first;
-        auto ct = ctx->stop_tables.find(n);
-        if (ct == ctx->stop_tables.end()) {
-          std::vector<double> t((size_t)n + 1);
-          for (int c = 0; c <= n; c++) t[(size_t)c] = max_iterations_for(c, n > 0 ? n : 1, prm->probability);
-          ct = ctx->stop_tables.emplace(n, std::move(t)).first;
-        }
-        stop.insert(stop.end(), ct->second.begin(), ct->second.end());
-      }
-      stop_off[(size_t)p] = it->second;
-    }
-  }
+  std::vector<int64_t> stop_off;
+  osfm_stop_tables(ctx, offsets, n_pairs, prm->probability, 5, &stop, &stop_off);
   const int lo = prm->lo_iterations > 0 ? prm->lo_iterations : 1;
   // one device allocation for all work buffers of the batch (hipMalloc / hipFree are expensive and synchronising)
   const size_t cap5 = ((size_t)n_pairs * kMaxSlots + kWave - 1) / kWave * kWave;

@@ -1178,12 +1178,13 @@ OSFM_HD double relpose_error(const double* RT, const double* x0, const double* y
   normalise_bearing(y0, y);
   return relpose_error_unit(RT, x, y);
 }
-// ShouldStop (robust/robust_estimator.h:20-35) for MINIMAL_SAMPLES = 5: the bound depends only on (best inlier count, n,
-// probability) and goes through std::pow / std::log, so the HOST tabulates it with its libm for every possible count (n + 1
-// doubles per pair) and the kernel only looks it up -- the device math library cannot move a stopping decision.
-inline double max_iterations_for(int best_n, int n, double probability) {  // host only
+// ShouldStop (robust/robust_estimator.h:20-35) for MINIMAL_SAMPLES = 5 (relative pose) or 3 (relative rotation, relrot_core.h): the
+// bound depends only on (best inlier count, n, probability) and goes through std::pow / std::log, so the HOST tabulates it with its
+// libm for every possible count (n + 1 doubles per pair) and the kernel only looks it up -- the device math library cannot move a
+// stopping decision.
+inline double max_iterations_for(int best_n, int n, double probability, int minimal_samples = 5) {  // host only
   const double ratio = (double)best_n / (double)n;
-  double p1 = 1.0 - pow(ratio, 5.0);
+  double p1 = 1.0 - pow(ratio, (double)minimal_samples);
   if (p1 > 1.0 - kEps) p1 = 1.0 - kEps;
   return log(1.0 - probability) / log(p1);
 }

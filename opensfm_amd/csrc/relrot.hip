@@ -1,0 +1,187 @@
+// relrot.hip -- rotation-only LO-RANSAC for a batch of image pairs on gfx950: the ranking of reconstruction.compute_image_pairs.
+//
+// The numerics and the per-pair walk live in relrot_core.h (host + device), the GPU wave policy in gpu_wave.h; this file adds the
+// kernels and the C ABI.  One wavefront per pair: lane 0 draws the samples of the next block of iterations, every lane solves one 3-point model,
+// all lanes score each model over the pair's correspondences (ballot + popcount, inlier list compacted in order), and the same
+// launch ends with the rotation-only inlier count and the reconstructability score.
+#include <math.h>
+
+#include <algorithm>
+#include <unordered_map>
+#include <vector>
+
+#include "gpu_wave.h"
+#include "osfm_internal.h"
+#include "relrot_core.h"
+
+using namespace osfm_rr;
+using osfm_rp::DevBuf;
+using osfm_rp::GpuWave;
+using osfm_rp::kWave;
+
+namespace {
+
+static_assert(sizeof(RelrotOut) == sizeof(osfm_relrot_result), "RelrotOut must mirror osfm_relrot_result");
+
+__global__ __launch_bounds__(kWave) void rr_pairs_kernel(RelrotArgs A, int n_pairs) {
+  const int p = (int)blockIdx.x;
+  if (p >= n_pairs) return;
+  __shared__ RelrotShared sh;
+  GpuWave w{(int)threadIdx.x};
+  relrot_pair(w, sh, A, p);
+}
+
+// bearings of both sides of every pair from normalised image coordinates: one workgroup per pair, the pair's two cameras from the
+// camera table (osfm_rp::pixel_bearing_generic, the code of osfm_pixel_bearings)
+__global__ __launch_bounds__(256) void rr_bearings_kernel(const double *__restrict__ p1, const double *__restrict__ p2, const int64_t *offsets,
+                                                          const int32_t *pair_cams, const int32_t *cam_model, const double *cam_params,
+                                                          double *b1, double *b2) {
+  const int p = (int)blockIdx.x;
+  const int64_t o = offsets[p], e = offsets[p + 1];
+  const int c1 = pair_cams[2 * p], c2 = pair_cams[2 * p + 1];
+  const int m1 = cam_model[c1], m2 = cam_model[c2];
+  const double *par1 = cam_params + 16 * (size_t)c1, *par2 = cam_params + 16 * (size_t)c2;
+  for (int64_t i = o + threadIdx.x; i < e; i += blockDim.x) {
+    osfm_rp::pixel_bearing_generic(m1, par1, p1[2 * i], p1[2 * i + 1], b1 + 3 * i);
+    osfm_rp::pixel_bearing_generic(m2, par2, p2[2 * i], p2[2 * i + 1], b2 + 3 * i);
+  }
+}
+
+int check_args(const int64_t *offsets, int n_pairs, const osfm_relrot_params *prm, const char *who) {
+  OSFM_REQUIRE(offsets && prm, OSFM_E_INVALID, "%s: null argument", who);
+  OSFM_REQUIRE(n_pairs >= 0, OSFM_E_INVALID, "%s: n_pairs < 0", who);
+  OSFM_REQUIRE(prm->iterations >= 0 && prm->lo_iterations >= 0 && prm->threshold > 0 && prm->probability > 0 && prm->probability < 1,
+               OSFM_E_INVALID, "%s: bad parameters", who);
+  if (n_pairs == 0) return OSFM_OK;
+  OSFM_REQUIRE(offsets[0] == 0, OSFM_E_INVALID, "%s: offsets[0] must be 0", who);
+  for (int p = 0; p < n_pairs; p++) {
+    OSFM_REQUIRE(offsets[p + 1] - offsets[p] >= kMinimalSamples, OSFM_E_INVALID,
+                 "%s: pair %d has %lld correspondences (at least 3 are needed to draw a sample)", who, p, (long long)(offsets[p + 1] - offsets[p]));
+    OSFM_REQUIRE(offsets[p + 1] - offsets[p] <= (1 << 24), OSFM_E_INVALID, "%s: pair %d is too large", who, p);
+  }
+  return OSFM_OK;
+}
+
+// The batch on device-resident bearings; results and mask copied to the host.  The caller holds the context lock.
+int run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *d_b2, const int64_t *d_off, const int64_t *offsets, int n_pairs,
+               const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, bool timed_from_ev0, double *kernel_ms) {
+  const int64_t total = offsets[n_pairs];
+  RngTable rng;
+  {
+    const int rc = osfm_rng_table(ctx, &rng);
+    if (rc != OSFM_OK) return rc;
+  }
+  std::vector<double> stop;
+  std::vector<int64_t> stop_off;
+  osfm_stop_tables(ctx, offsets, n_pairs, prm->probability, kMinimalSamples, &stop, &stop_off);
+  bool any_large = false;
+  for (int p = 0; p < n_pairs && !any_large; p++) any_large = offsets[p + 1] - offsets[p] > kLdsInliers;
+  const size_t sizes[] = {stop.size() * 8, stop_off.size() * 8, any_large ? (size_t)total * 4 : 4, (size_t)n_pairs * sizeof(RelrotOut),
+                          mask ? (size_t)total : 1, 16};
+  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
+  size_t offs[kBuffers], arena_bytes = 0;
+  for (int i = 0; i < kBuffers; i++) {
+    offs[i] = arena_bytes;
+    arena_bytes += (sizes[i] + 255) / 256 * 256;
+  }
+  OsfmPoolBuf arena;
+  OSFM_HIP(arena.alloc(ctx, arena_bytes));
+  char *base = (char *)arena.p;
+  double *d_stop = (double *)(base + offs[0]);
+  int64_t *d_stopoff = (int64_t *)(base + offs[1]);
+  int *d_scratch = (int *)(base + offs[2]);
+  RelrotOut *d_out = (RelrotOut *)(base + offs[3]);
+  uint8_t *d_mask = mask ? (uint8_t *)(base + offs[4]) : nullptr;
+  int *d_flag = (int *)(base + offs[5]);
+  OSFM_HIP(hipMemcpyAsync(d_stop, stop.data(), stop.size() * 8, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_stopoff, stop_off.data(), stop_off.size() * 8, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemsetAsync(d_flag, 0, 16, st));
+  RelrotArgs A{d_b1, d_b2, d_off, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), prm->inlier_chord, (int)prm->iterations, (int)prm->use_lo,
+               (int)prm->lo_iterations, (int)prm->use_iteration_reduction, d_scratch, d_out, d_mask, d_flag};
+  if (!timed_from_ev0) OSFM_HIP(hipEventRecord(ctx->ev[0], st));
+  hipLaunchKernelGGL(rr_pairs_kernel, dim3((unsigned)n_pairs), dim3(kWave), 0, st, A, n_pairs);
+  OSFM_HIP(hipGetLastError());
+  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
+  int flag = 0;
+  OSFM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(results, d_out, (size_t)n_pairs * sizeof(RelrotOut), hipMemcpyDeviceToHost, st));
+  if (mask) OSFM_HIP(hipMemcpyAsync(mask, d_mask, (size_t)total, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipStreamSynchronize(st));
+  OSFM_REQUIRE(flag == 0, OSFM_E_UNSUPPORTED, "osfm_relrot_pairs: the tabulated mt19937 stream is too short for this input");
+  if (kernel_ms) {
+    float ms = 0.f;
+    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    *kernel_ms = ms;
+  }
+  return OSFM_OK;
+}
+
+}  // namespace
+
+extern "C" int osfm_relrot_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const int64_t *offsets, int n_pairs,
+                                 const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, double *kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "osfm_relrot_pairs: null context");
+  {
+    const int rc = check_args(offsets, n_pairs, prm, "osfm_relrot_pairs");
+    if (rc != OSFM_OK) return rc;
+  }
+  if (n_pairs == 0) return OSFM_OK;
+  OSFM_REQUIRE(b1 && b2 && results, OSFM_E_INVALID, "osfm_relrot_pairs: null bearings / results");
+  const int64_t total = offsets[n_pairs];
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf d_b1, d_b2, d_off;
+  OSFM_HIP(d_b1.alloc((size_t)total * 24));
+  OSFM_HIP(d_b2.alloc((size_t)total * 24));
+  OSFM_HIP(d_off.alloc((size_t)(n_pairs + 1) * 8));
+  OSFM_HIP(hipMemcpyAsync(d_b1.p, b1, (size_t)total * 24, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_b2.p, b2, (size_t)total * 24, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+  return run_device(ctx, st, d_b1.as<double>(), d_b2.as<double>(), d_off.as<int64_t>(), offsets, n_pairs, prm, results, mask, false, kernel_ms);
+}
+
+extern "C" int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, const int64_t *offsets, int n_pairs,
+                                        const int32_t *pair_cams, const int32_t *cam_model, const double *cam_params, int n_cams,
+                                        const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, double *kernel_ms) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "osfm_relrot_pairs_pixels: null context");
+  {
+    const int rc = check_args(offsets, n_pairs, prm, "osfm_relrot_pairs_pixels");
+    if (rc != OSFM_OK) return rc;
+  }
+  if (n_pairs == 0) return OSFM_OK;
+  OSFM_REQUIRE(p1 && p2 && results && pair_cams && cam_model && cam_params && n_cams > 0, OSFM_E_INVALID,
+               "osfm_relrot_pairs_pixels: null argument");
+  for (int c = 0; c < n_cams; c++)
+    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID,
+                 "osfm_relrot_pairs_pixels: camera %d has model %d", c, cam_model[c]);
+  for (int p = 0; p < n_pairs; p++)
+    OSFM_REQUIRE(pair_cams[2 * p] >= 0 && pair_cams[2 * p] < n_cams && pair_cams[2 * p + 1] >= 0 && pair_cams[2 * p + 1] < n_cams, OSFM_E_INVALID,
+                 "osfm_relrot_pairs_pixels: pair %d names a camera outside the table", p);
+  const int64_t total = offsets[n_pairs];
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  DevBuf d_p1, d_p2, d_b1, d_b2, d_off, d_pc, d_cm, d_cp;
+  OSFM_HIP(d_p1.alloc((size_t)total * 16));
+  OSFM_HIP(d_p2.alloc((size_t)total * 16));
+  OSFM_HIP(d_b1.alloc((size_t)total * 24));
+  OSFM_HIP(d_b2.alloc((size_t)total * 24));
+  OSFM_HIP(d_off.alloc((size_t)(n_pairs + 1) * 8));
+  OSFM_HIP(d_pc.alloc((size_t)n_pairs * 8));
+  OSFM_HIP(d_cm.alloc((size_t)n_cams * 4));
+  OSFM_HIP(d_cp.alloc((size_t)n_cams * 16 * 8));
+  OSFM_HIP(hipMemcpyAsync(d_p1.p, p1, (size_t)total * 16, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_p2.p, p2, (size_t)total * 16, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_off.p, offsets, (size_t)(n_pairs + 1) * 8, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_pc.p, pair_cams, (size_t)n_pairs * 8, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_cm.p, cam_model, (size_t)n_cams * 4, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_cp.p, cam_params, (size_t)n_cams * 16 * 8, hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipEventRecord(ctx->ev[0], st));  // the kernel time includes the bearings
+  hipLaunchKernelGGL(rr_bearings_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, d_p1.as<double>(), d_p2.as<double>(), d_off.as<int64_t>(),
+                     d_pc.as<int32_t>(), d_cm.as<int32_t>(), d_cp.as<double>(), d_b1.as<double>(), d_b2.as<double>());
+  OSFM_HIP(hipGetLastError());
+  return run_device(ctx, st, d_b1.as<double>(), d_b2.as<double>(), d_off.as<int64_t>(), offsets, n_pairs, prm, results, mask, true, kernel_ms);
+}

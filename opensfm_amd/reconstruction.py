@@ -1,0 +1,135 @@
+"""Drop-ins for the first phase of ``opensfm reconstruct``: ranking the candidate initial pairs (``reconstruction.compute_image_pairs``,
+``opensfm/reconstruction.py:208-244``) with one batched rotation-only LO-RANSAC on the GPU (``relrot.hip``).
+
+``compute_image_pairs(track_dict, data)`` takes what ``tracking.all_common_tracks_with_features`` returns, concatenates the pairs'
+normalised image coordinates in item order, computes the bearings and runs ``pyrobust.ransac_relative_rotation`` for every pair in
+one call, counts the rotation-only inliers and the reconstructability on the device, and sorts on the host exactly as the reference
+does (``np.argsort(-np.array(score))``)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ._lib import RelrotParams, RelrotResult, check, default_context, load
+from .matching import camera_parameters
+
+
+def _fptr(a: np.ndarray, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def _params(threshold: float, iterations: int, probability: float, use_lo: bool, lo_iterations: int, use_iteration_reduction: bool,
+            inlier_chord: float) -> RelrotParams:
+    return RelrotParams(float(threshold), float(probability), float(inlier_chord), int(iterations), int(bool(use_lo)), int(lo_iterations),
+                        int(bool(use_iteration_reduction)))
+
+
+def _results(res, n_pairs: int) -> List[Dict[str, Any]]:
+    out = []
+    for p in range(n_pairs):
+        r = res[p]
+        out.append({"model": np.array(r.model).reshape(3, 3), "lo_model": np.array(r.lo_model).reshape(3, 3), "score": r.score,
+                    "iterations": r.iterations, "n_rotation_inliers": r.n_rotation_inliers, "reconstructability": r.reconstructability})
+    return out
+
+
+def relrot_pairs(b1: np.ndarray, b2: np.ndarray, offsets: Sequence[int], threshold: float, iterations: int = 1000, probability: float = 0.99,
+                 use_lo: bool = True, lo_iterations: int = 10, use_iteration_reduction: bool = True, inlier_chord: float = 0.0,
+                 ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, float]:
+    """Batched ``pyrobust.ransac_relative_rotation`` on bearings (``osfm_relrot_pairs``): pair p owns rows offsets[p]:offsets[p+1] of
+    b1 / b2.  -> (per-pair dicts, mask of the RANSAC inliers over all rows, kernel milliseconds)."""
+    ctx = ctx or default_context()
+    b1 = np.ascontiguousarray(b1, np.float64).reshape(-1, 3)
+    b2 = np.ascontiguousarray(b2, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(b1) != len(b2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(b1)):
+        raise ValueError("relrot_pairs: b1 / b2 / offsets do not agree")
+    prm = _params(threshold, iterations, probability, use_lo, lo_iterations, use_iteration_reduction, inlier_chord)
+    res = (RelrotResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(b1), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_relrot_pairs(ctx.handle, _fptr(b1, C.c_double), _fptr(b2, C.c_double), _fptr(off, C.c_int64), n_pairs, C.byref(prm), res,
+                                   _fptr(mask, C.c_uint8), C.byref(ms)), "osfm_relrot_pairs")
+    return _results(res, n_pairs), mask[: len(b1)].astype(bool), ms.value
+
+
+def relrot_pairs_pixels(p1: np.ndarray, p2: np.ndarray, offsets: Sequence[int], pair_cams: np.ndarray, cam_model: np.ndarray,
+                        cam_params: np.ndarray, threshold: float, iterations: int = 1000, probability: float = 0.99, use_lo: bool = True,
+                        lo_iterations: int = 10, inlier_chord: float = 0.0, with_mask: bool = False,
+                        ctx=None) -> Tuple[List[Dict[str, Any]], Optional[np.ndarray], float]:
+    """``osfm_relrot_pairs_pixels``: the same from normalised image coordinates, the bearings computed on the device with the cameras
+    pair_cams[p] = (camera of side 1, camera of side 2) of the table cam_model (n_cams) / cam_params (n_cams x 16)."""
+    ctx = ctx or default_context()
+    p1 = np.ascontiguousarray(np.asarray(p1, np.float64)[:, :2])
+    p2 = np.ascontiguousarray(np.asarray(p2, np.float64)[:, :2])
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(p1) != len(p2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(p1)):
+        raise ValueError("relrot_pairs_pixels: p1 / p2 / offsets do not agree")
+    pc = np.ascontiguousarray(pair_cams, np.int32)
+    cm = np.ascontiguousarray(cam_model, np.int32)
+    cp = np.ascontiguousarray(cam_params, np.float64)
+    if pc.shape != (n_pairs, 2) or cm.ndim != 1 or cp.shape != (len(cm), 16):
+        raise ValueError(f"relrot_pairs_pixels: pair_cams must be ({n_pairs}, 2) and cam_params ({len(cm)}, 16) for cam_model of length "
+                         f"{len(cm)}; got {pc.shape}, {cp.shape}")
+    prm = _params(threshold, iterations, probability, use_lo, lo_iterations, True, inlier_chord)
+    res = (RelrotResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(p1), 1), np.uint8) if with_mask else None
+    ms = C.c_double(0.0)
+    check(load().osfm_relrot_pairs_pixels(ctx.handle, _fptr(p1, C.c_double), _fptr(p2, C.c_double), _fptr(off, C.c_int64), n_pairs,
+                                          _fptr(pc, C.c_int32), _fptr(cm, C.c_int32), _fptr(cp, C.c_double), len(cm), C.byref(prm), res,
+                                          _fptr(mask, C.c_uint8) if with_mask else None, C.byref(ms)), "osfm_relrot_pairs_pixels")
+    return _results(res, n_pairs), (mask[: len(p1)].astype(bool) if with_mask else None), ms.value
+
+
+def pairwise_reconstructability(common_tracks: int, rotation_inliers: int) -> float:
+    """Likeliness of an image pair giving a good initial reconstruction (``reconstruction.py:193-200``)."""
+    outliers = common_tracks - rotation_inliers
+    outlier_ratio = float(outliers) / common_tracks
+    if outlier_ratio >= 0.3:
+        return outliers
+    else:
+        return 0
+
+
+def _camera_table(track_dict, data) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """pair_cams (n_pairs x 2), cam_model, cam_params of the cameras the pairs' images use (``_pair_reconstructability_arguments``)."""
+    cameras = data.load_camera_models()
+    index: Dict[str, int] = {}
+    models: List[int] = []
+    params: List[np.ndarray] = []
+    pair_cams = np.zeros((len(track_dict), 2), np.int32)
+    for k, (im1, im2) in enumerate(track_dict.keys()):
+        for side, im in enumerate((im1, im2)):
+            key = data.load_exif(im)["camera"]
+            if key not in index:
+                model, par = camera_parameters(cameras[key])
+                index[key] = len(models)
+                models.append(model)
+                params.append(par)
+            pair_cams[k, side] = index[key]
+    return pair_cams, np.array(models, np.int32), np.array(params, np.float64).reshape(-1, 16)
+
+
+def compute_image_pairs(track_dict: Dict[Tuple[str, str], Any], data, ctx=None) -> List[Tuple[str, str]]:
+    """All matched image pairs sorted by reconstructability (``reconstruction.py:208-220``): same arguments, same return."""
+    if not track_dict:
+        return []
+    threshold = 4 * data.config["five_point_algo_threshold"]
+    pair_cams, cam_model, cam_params = _camera_table(track_dict, data)
+    values = list(track_dict.values())
+    p1 = np.concatenate([np.asarray(v[1], np.float64).reshape(-1, 2) for v in values])
+    p2 = np.concatenate([np.asarray(v[2], np.float64).reshape(-1, 2) for v in values])
+    off = np.r_[0, np.cumsum([len(v[1]) for v in values])].astype(np.int64)
+    # two_view_reconstruction_rotation_only: relative_pose_ransac_rotation_only(b1, b2, threshold, 1000, 0.999) -- the 0.999 is not
+    # passed on (multiview.py:520-540 sets only the iterations), so the probability is the default 0.99
+    res, _, _ = relrot_pairs_pixels(p1, p2, off, pair_cams, cam_model, cam_params, threshold, iterations=1000, probability=0.99, use_lo=True,
+                                    lo_iterations=10, inlier_chord=threshold, ctx=ctx)
+    keys = list(track_dict.keys())
+    pairs = [keys[k] for k, r in enumerate(res) if r["reconstructability"] > 0]
+    score = [int(r["reconstructability"]) for r in res if r["reconstructability"] > 0]
+    order = np.argsort(-np.array(score))
+    return [pairs[o] for o in order]

@@ -1,0 +1,378 @@
+"""The rotation-only LO-RANSAC of compute_image_pairs (opensfm_amd/csrc/relrot_core.h), compiled for the host with loops in place of
+lanes (tests/native/relrot_host.cpp): the header's walk against an independent sequential restatement of
+Estimate<RansacScoring, RelativeRotation> on this toolchain's std::mt19937, bit for bit; the SVD of RotationBetweenPoints; and,
+where the reference is mounted, the reference's own robust_estimator.h around the same model numerics and its
+test_outliers_relative_rotation_ransac with pyrobust served by the host build."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "opensfm_amd", "csrc")
+REF = "/root/reference/opensfm"
+OUT = os.path.join(HERE, "native", "_build")
+
+
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
+
+
+def _build(name, src, extra=()):
+    os.makedirs(OUT, exist_ok=True)
+    so = os.path.join(OUT, name)
+    deps = [src] + [os.path.join(CSRC, h) for h in ("relrot_core.h", "relpose_core.h", "relpose_rounds.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-std=c++17", *extra, "-o", so, src])
+    return C.CDLL(so)
+
+
+def build_host():
+    lib = _build("relrot_host.so", os.path.join(HERE, "native", "relrot_host.cpp"))
+    lib.host_relrot_pairs.restype = C.c_int
+    lib.host_relrot_pairs.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.c_double, C.c_double,
+                                      C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint8)]
+    lib.host_sequential_estimate.restype = C.c_int
+    lib.host_sequential_estimate.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]
+    lib.host_rotation_error.restype = C.c_double
+    lib.host_rotation_chord.restype = C.c_double
+    return lib
+
+
+@pytest.fixture(scope="module")
+def host():
+    return build_host()
+
+
+class Result(C.Structure):  # relrot_core.h RelrotOut == osfm_relrot_result
+    _fields_ = [("model", C.c_double * 9), ("lo_model", C.c_double * 9), ("score", C.c_int32), ("iterations", C.c_int32),
+                ("n_rotation_inliers", C.c_int32), ("reconstructability", C.c_int32)]
+
+
+def host_pairs(lib, b1, b2, off, threshold, probability=0.99, chord=0.0, iterations=1000, use_lo=1, lo_iterations=10, use_reduction=1):
+    """relrot_core.h's walk on the host: (list of Result, mask)"""
+    b1 = np.ascontiguousarray(b1, np.float64)
+    b2 = np.ascontiguousarray(b2, np.float64)
+    off = np.ascontiguousarray(off, np.int64)
+    n_pairs = len(off) - 1
+    res = (Result * max(n_pairs, 1))()
+    mask = np.zeros(max(int(off[-1]), 1), np.uint8)
+    rc = lib.host_relrot_pairs(_p(b1, C.c_double), _p(b2, C.c_double), _p(off, C.c_int64), n_pairs, threshold, probability, chord, iterations,
+                               use_lo, lo_iterations, use_reduction, C.cast(res, C.c_void_p), _p(mask, C.c_uint8))
+    assert rc == 0, rc
+    return [res[p] for p in range(n_pairs)], mask[: int(off[-1])].astype(bool)
+
+
+def sequential(lib, b1, b2, threshold, probability=0.99, iterations=1000, use_lo=1, lo_iterations=10, use_reduction=1):
+    b1 = np.ascontiguousarray(b1, np.float64)
+    b2 = np.ascontiguousarray(b2, np.float64)
+    n = len(b1)
+    m, lo, inl, it = np.zeros(9), np.zeros(9), np.zeros(max(n, 1), np.int32), np.zeros(1, np.int32)
+    s = lib.host_sequential_estimate(_p(b1, C.c_double), _p(b2, C.c_double), n, threshold, probability, iterations, use_lo, lo_iterations,
+                                     use_reduction, _p(m, C.c_double), _p(lo, C.c_double), _p(inl, C.c_int32), _p(it, C.c_int32))
+    return s, m, lo, inl[:s].copy(), int(it[0])
+
+
+def _rot(rng, scale=0.3):
+    r = rng.normal(0, scale, 3)
+    th = np.linalg.norm(r)
+    K = np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]]) / max(th, 1e-300)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+def make_problem(rng, n, outliers=0.3, noise=1e-3, baseline=0.0, exact=False, duplicates=0):
+    """b1 / b2 (n x 3 unit bearings, first / second) of a two-view scene: a rotation plus, if baseline > 0, a translation."""
+    R = _rot(rng)
+    X = np.c_[rng.uniform(-2, 2, n), rng.uniform(-2, 2, n), rng.uniform(4, 9, n)]
+    t = rng.normal(0, 1, 3)
+    t *= baseline / np.linalg.norm(t)
+    X2 = X @ R.T + t
+    if not exact:
+        X = X + rng.normal(0, noise, X.shape)
+        X2 = X2 + rng.normal(0, noise, X.shape)
+    bad = rng.random(n) < outliers
+    X2[bad] = np.c_[rng.uniform(-2, 2, bad.sum()), rng.uniform(-2, 2, bad.sum()), rng.uniform(4, 9, bad.sum())]
+    b1 = X / np.linalg.norm(X, axis=1, keepdims=True)
+    b2 = X2 / np.linalg.norm(X2, axis=1, keepdims=True)
+    if duplicates and n > 1:
+        src = rng.integers(0, n, duplicates)
+        dst = rng.integers(0, n, duplicates)
+        b1[dst], b2[dst] = b1[src], b2[src]
+    return np.ascontiguousarray(b1), np.ascontiguousarray(b2)
+
+
+def problem_set(seed=0, count=200, n_max=5000):
+    """~count problems: N from 3 to n_max, outlier fractions 0 .. 90 %, exact pure rotations, duplicated bearings, all-inlier sets"""
+    rng = np.random.default_rng(seed)
+    out = []
+    sizes = [3, 4, 5, 6, 7, 8, 12, 20, 50, 64, 65, 100, 300, 1000, n_max]
+    for k in range(count):
+        n = sizes[k] if k < len(sizes) else int(np.exp(rng.uniform(np.log(3), np.log(n_max))))
+        kind = k % 5
+        if kind == 0:
+            out.append(make_problem(rng, n, outliers=0.0, exact=True))  # exact pure rotation: stops early
+        elif kind == 1:
+            out.append(make_problem(rng, n, outliers=rng.uniform(0, 0.9)))
+        elif kind == 2:
+            out.append(make_problem(rng, n, outliers=rng.uniform(0, 0.5), baseline=rng.uniform(0.2, 1.5)))
+        elif kind == 3:
+            out.append(make_problem(rng, n, outliers=rng.uniform(0, 0.6), duplicates=max(1, n // 5)))
+        else:
+            out.append(make_problem(rng, n, outliers=0.0, noise=2e-4))
+    return out
+
+
+def test_walk_equals_sequential_estimate_bit_for_bit(host):
+    probs = problem_set()
+    b1 = np.concatenate([p[0] for p in probs])
+    b2 = np.concatenate([p[1] for p in probs])
+    off = np.r_[0, np.cumsum([len(p[0]) for p in probs])]
+    thr = 0.016
+    res, mask = host_pairs(host, b1, b2, off, thr)
+    early = 0
+    for k, (x, y) in enumerate(probs):
+        s, m, lo, inl, it = sequential(host, x, y, thr)
+        r = res[k]
+        assert r.score == s, k
+        assert r.iterations == it, k
+        assert np.array_equal(np.array(r.model), m) and np.array_equal(np.array(r.lo_model), lo), k
+        assert np.array_equal(np.flatnonzero(mask[off[k]: off[k + 1]]), inl), k
+        early += it < 1000
+    assert early >= 60  # the all-inlier sets stop early
+
+
+@pytest.mark.parametrize("use_lo,lo_iterations,use_reduction,iterations,probability",
+                         [(0, 10, 1, 1000, 0.99), (1, 3, 1, 200, 0.999), (1, 10, 0, 150, 0.99), (1, 0, 1, 1000, 0.5)])
+def test_walk_equals_sequential_estimate_other_parameters(host, use_lo, lo_iterations, use_reduction, iterations, probability):
+    probs = problem_set(seed=3, count=40, n_max=800)
+    b1 = np.concatenate([p[0] for p in probs])
+    b2 = np.concatenate([p[1] for p in probs])
+    off = np.r_[0, np.cumsum([len(p[0]) for p in probs])]
+    res, mask = host_pairs(host, b1, b2, off, 0.01, probability, 0.0, iterations, use_lo, lo_iterations, use_reduction)
+    for k, (x, y) in enumerate(probs):
+        s, m, lo, inl, it = sequential(host, x, y, 0.01, probability, iterations, use_lo, lo_iterations, use_reduction)
+        assert (res[k].score, res[k].iterations) == (s, it), k
+        assert np.array_equal(np.array(res[k].model), m) and np.array_equal(np.array(res[k].lo_model), lo), k
+        assert np.array_equal(np.flatnonzero(mask[off[k]: off[k + 1]]), inl), k
+
+
+def test_rotation_inlier_count_and_reconstructability(host):
+    rng = np.random.default_rng(5)
+    probs = [make_problem(rng, n, outliers=o, baseline=bl) for n, o, bl in [(60, 0.0, 0.0), (300, 0.5, 0.0), (200, 0.1, 1.0), (50, 0.35, 0.0)]]
+    b1 = np.concatenate([p[0] for p in probs])
+    b2 = np.concatenate([p[1] for p in probs])
+    off = np.r_[0, np.cumsum([len(p[0]) for p in probs])]
+    res, _ = host_pairs(host, b1, b2, off, 0.016, chord=0.016)
+    for k, (x, y) in enumerate(probs):
+        R = np.array(res[k].lo_model).reshape(3, 3).T
+        d = np.linalg.norm((R @ y.T).T - x, axis=1)
+        n_in = int((d < 0.016).sum())
+        assert abs(res[k].n_rotation_inliers - n_in) <= int((np.abs(d - 0.016) < 1e-15).sum()), k
+        outl = len(x) - res[k].n_rotation_inliers
+        assert res[k].reconstructability == (outl if outl / len(x) >= 0.3 else 0)
+
+
+def _sample_M(rng, count, rank2=False):
+    b1 = rng.normal(size=(count, 3))
+    b2 = b1 @ _rot(rng, 1.0).T + rng.normal(0, 0.05, (count, 3))
+    q = b1 - b1.mean(0)
+    p = b2 - b2.mean(0)
+    return q.T @ p
+
+
+def test_svd_full_rank_is_the_polar_factor(host):
+    rng = np.random.default_rng(1)
+    for _ in range(300):
+        M = np.ascontiguousarray(_sample_M(rng, 8))
+        U, S, V = np.zeros(9), np.zeros(3), np.zeros(9)
+        host.host_jacobi_svd3(_p(M, C.c_double), _p(U, C.c_double), _p(S, C.c_double), _p(V, C.c_double))
+        U, V = U.reshape(3, 3), V.reshape(3, 3)
+        assert np.allclose(U @ np.diag(S) @ V.T, M, atol=1e-12 * np.abs(M).max())
+        assert np.all(np.diff(S) <= 0)
+        u, s, vt = np.linalg.svd(M)
+        polar = u @ vt
+        assert np.abs(U @ V.T - polar).max() < 1e-12
+        # the model: R = U V^T (negated when det < 0), transposed
+        b1 = rng.normal(size=(10, 3))
+        b2 = b1 @ _rot(rng, 1.0).T + rng.normal(0, 0.05, (10, 3))
+        idx = np.arange(10, dtype=np.int32)
+        model = np.zeros(9)
+        host.host_rotation_model(_p(np.ascontiguousarray(b1), C.c_double), _p(np.ascontiguousarray(b2), C.c_double), _p(idx, C.c_int32), 10,
+                                 _p(model, C.c_double), None)
+        q, pp = b1 - b1.mean(0), b2 - b2.mean(0)
+        u, s, vt = np.linalg.svd(q.T @ pp)
+        R = u @ vt
+        R = -R if np.linalg.det(R) < 0 else R
+        assert np.abs(model.reshape(3, 3) - R.T).max() < 1e-12
+
+
+def negation_fraction(host, rng, count=4000, fov=None):
+    """fraction of minimal (3-point) hypotheses of random rotations that take the det < 0 branch, counted by the models' own flags:
+    (this header's SVD, osfm_rp::svd3).  fov=None: bearings anywhere on the sphere; fov=a: within +-a rad of the optical axis."""
+    neg_e = neg_s = 0
+    idx = np.arange(3, dtype=np.int32)
+    for _ in range(count):
+        if fov is None:
+            b1 = rng.normal(size=(3, 3))
+        else:
+            b1 = np.c_[np.tan(rng.uniform(-fov, fov, (3, 2))), np.ones(3)]
+        b1 /= np.linalg.norm(b1, axis=1, keepdims=True)
+        b2 = b1 @ _rot(rng, 0.3 if fov is not None else 1.0).T
+        b1, b2 = np.ascontiguousarray(b1), np.ascontiguousarray(b2)
+        m = np.zeros(9)
+        neg = C.c_int(0)
+        host.host_rotation_model_svd3(_p(b1, C.c_double), _p(b2, C.c_double), _p(idx, C.c_int32), 3, _p(m, C.c_double), C.byref(neg))
+        neg_s += neg.value
+        host.host_rotation_model(_p(b1, C.c_double), _p(b2, C.c_double), _p(idx, C.c_int32), 3, _p(m, C.c_double), C.byref(neg))
+        neg_e += neg.value
+    return neg_e / count, neg_s / count
+
+
+def _M_as_the_header(b1, b2):
+    """M of rotation_model with its operation order (the null-space signs of a rank-2 M follow its rounding)"""
+    n = len(b1)
+    qa, pa = [0.0] * 3, [0.0] * 3
+    for k in range(n):
+        for a in range(3):
+            qa[a] += float(b1[k, a])
+            pa[a] += float(b2[k, a])
+    qa, pa = [v / n for v in qa], [v / n for v in pa]
+    M = np.zeros((3, 3))
+    for k in range(n):
+        q = [float(b1[k, a]) - qa[a] for a in range(3)]
+        p = [float(b2[k, a]) - pa[a] for a in range(3)]
+        for i in range(3):
+            for j in range(3):
+                M[i, j] += q[i] * p[j]
+    return M
+
+
+def test_svd_rank2_gives_plus_or_minus_u_vt_never_the_flip(host):
+    rng = np.random.default_rng(2)
+    kept = negated = 0
+    for _ in range(500):
+        b1 = rng.normal(size=(3, 3))
+        b1 /= np.linalg.norm(b1, axis=1, keepdims=True)
+        b2 = np.ascontiguousarray(b1 @ _rot(rng, 1.0).T)
+        b1 = np.ascontiguousarray(b1)
+        M = np.ascontiguousarray(_M_as_the_header(b1, b2))
+        U, S, V = np.zeros(9), np.zeros(3), np.zeros(9)
+        host.host_jacobi_svd3(_p(M, C.c_double), _p(U, C.c_double), _p(S, C.c_double), _p(V, C.c_double))
+        U, V = U.reshape(3, 3), V.reshape(3, 3)
+        assert S[2] < 1e-12 * S[0]
+        R = U @ V.T
+        m = np.zeros(9)
+        idx = np.arange(3, dtype=np.int32)
+        neg = C.c_int(-1)
+        host.host_rotation_model(_p(b1, C.c_double), _p(b2, C.c_double), _p(idx, C.c_int32), 3, _p(m, C.c_double), C.byref(neg))
+        got = m.reshape(3, 3).T
+        assert abs(np.linalg.det(got) - 1.0) < 1e-12
+        assert neg.value == int(np.linalg.det(R) < 0)  # the flag negation_fraction counts
+        if np.linalg.det(R) < 0:
+            assert np.abs(got + R).max() < 1e-12  # the whole matrix negated
+            negated += 1
+        else:
+            assert np.abs(got - R).max() < 1e-12
+            kept += 1
+        flip = U @ np.diag([1.0, 1.0, -1.0]) @ V.T  # the textbook fix: never what RotationBetweenPoints returns
+        if np.linalg.det(flip) > 0:
+            assert np.abs(got - flip).max() > 1e-3
+    assert kept > 0 and negated > 0
+    for fov in (None, 0.5):
+        fe, fs = negation_fraction(host, rng, 2000, fov)
+        assert 0.3 < fe < 0.7 and 0.3 < fs < 0.7, (fov, fe, fs)
+
+
+def test_error_and_chord_operation_order(host):
+    rng = np.random.default_rng(4)
+    for _ in range(100):
+        m = np.ascontiguousarray(_rot(rng, 1.0)).reshape(-1)
+        x, y = np.ascontiguousarray(rng.normal(size=3)), np.ascontiguousarray(rng.normal(size=3))
+        M = m.reshape(3, 3)
+        v = [(M[r, 0] * x[0] + M[r, 1] * x[1]) + M[r, 2] * x[2] for r in range(3)]
+        e = 1.0 - ((v[0] * y[0] + v[1] * y[1]) + v[2] * y[2])
+        assert host.host_rotation_error(_p(m, C.c_double), _p(x, C.c_double), _p(y, C.c_double)) == e
+        d = [((M[0, r] * y[0] + M[1, r] * y[1]) + M[2, r] * y[2]) - x[r] for r in range(3)]
+        assert host.host_rotation_chord(_p(m, C.c_double), _p(x, C.c_double), _p(y, C.c_double)) == np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+
+
+# ---- against the reference's own code, where it is mounted ----
+need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is not mounted")
+
+
+@need_ref
+def test_walk_equals_reference_estimator_template(host):
+    ref = _build("relrot_ref.so", os.path.join(HERE, "native", "relrot_ref_adapter.cpp"),
+                 ["-I", os.path.join(ROOT, "oracle", "ref_adapters", "stubs"), "-I", os.path.join(REF, "src", "robust")])
+    ref.ref_ransac_relative_rotation.restype = C.c_int
+    probs = problem_set(seed=9, count=60, n_max=2000)
+    b1 = np.concatenate([p[0] for p in probs])
+    b2 = np.concatenate([p[1] for p in probs])
+    off = np.r_[0, np.cumsum([len(p[0]) for p in probs])]
+    res, mask = host_pairs(host, b1, b2, off, 0.016)
+    for k, (x, y) in enumerate(probs):
+        m, lo, inl = np.zeros(9), np.zeros(9), np.zeros(len(x), np.int32)
+        s = ref.ref_ransac_relative_rotation(_p(x, C.c_double), _p(y, C.c_double), len(x), C.c_double(0.016), 1000, C.c_double(0.99), 1, 10, 1,
+                                             _p(m, C.c_double), _p(lo, C.c_double), _p(inl, C.c_int32))
+        assert res[k].score == s, k
+        assert np.array_equal(np.array(res[k].model), m) and np.array_equal(np.array(res[k].lo_model), lo), k
+        assert np.array_equal(np.flatnonzero(mask[off[k]: off[k + 1]]), inl[:s]), k
+
+
+def host_pyrobust(lib):
+    """a pyrobust module whose ransac_relative_rotation is served by the host build"""
+    from opensfm_amd.compat import pyrobust as gpu_pyrobust
+
+    mod = types.ModuleType("pyrobust")
+    for name in ("RansacType", "RANSAC", "MSAC", "LMedS", "RobustEstimatorParams", "ScoreInfoMatrix3d"):
+        setattr(mod, name, getattr(gpu_pyrobust, name))
+
+    def ransac_relative_rotation(b1, b2, threshold, parameters, ransac_type=gpu_pyrobust.RANSAC):
+        assert int(ransac_type) == 0 and parameters.use_iteration_reduction
+        b1, b2 = np.asarray(b1, np.float64).reshape(-1, 3), np.asarray(b2, np.float64).reshape(-1, 3)
+        res, mask = host_pairs(lib, b1, b2, [0, len(b1)], threshold, parameters.probability, 0.0, parameters.iterations,
+                               int(parameters.use_local_optimization), 10, 1)
+        out = gpu_pyrobust.ScoreInfoMatrix3d()
+        out.score, out.model, out.lo_model = float(res[0].score), np.array(res[0].model).reshape(3, 3), np.array(res[0].lo_model).reshape(3, 3)
+        out.inliers_indices = [int(i) for i in np.flatnonzero(mask)]
+        return out
+
+    mod.ransac_relative_rotation = ransac_relative_rotation
+    return mod
+
+
+@need_ref
+def test_reference_outliers_relative_rotation_ransac(host):
+    """opensfm/test/test_robust.py::test_outliers_relative_rotation_ransac as the reference wrote it (compiled from its file, with the
+    helpers it calls), pyrobust = the host build; its fixture's bearings are replaced by this repo's own synthetic ones"""
+    import ast
+    from typing import List, Tuple
+
+    from numpy.typing import NDArray
+
+    path = os.path.join(REF, "test", "test_robust.py")
+    if not os.path.exists(path):
+        pytest.skip("the reference's test_robust.py is absent")
+    tree = ast.parse(open(path).read())
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "test_outliers_relative_rotation_ransac"]
+    if not fn:
+        pytest.skip("the reference has no test_outliers_relative_rotation_ransac")
+    used = {n.id for n in ast.walk(fn[0]) if isinstance(n, ast.Name)}
+    helpers = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in used]
+    ns = {"__name__": "ref_test_robust", "np": np, "pyrobust": host_pyrobust(host), "List": List, "Tuple": Tuple, "NDArray": NDArray,
+          "pygeometry": types.SimpleNamespace(Pose=object)}
+    exec(compile(ast.Module(body=helpers + fn, type_ignores=[]), path, "exec"), ns)
+    rng = np.random.default_rng(11)
+    pairs = []
+    for _ in range(4):
+        X = np.c_[rng.uniform(-2, 2, 300), rng.uniform(-2, 2, 300), rng.uniform(4, 9, 300)]
+        pairs.append((X, None, None, None))
+    np.random.seed(7)
+    ns["test_outliers_relative_rotation_ransac"](pairs)
