@@ -256,7 +256,7 @@ typedef struct {
                                 * itself (exact band by cyclic reduction + exact border, or constant cameras): that iterate is a direct solve
                                 * -- what Ceres' SPARSE_SCHUR stops at -- plus a line search, and lands at 1e-10 .. 1e-7 (conditioning x the
                                 * rounding of the explicit block inverses).  Default 1e-6: trajectories at 1e-6 and 1e-10 agree to 4e-16 in
-                                * the cost over 20 iterations at configs[4] (profiles/r06_pcg_tolerance.json).  <= pcg_tolerance: no such
+                                * the cost over 20 iterations at configs[4] (profiles/r06_pcg_direct_tolerance.json).  <= pcg_tolerance: no such
                                 * rule.  Inexact preconditioners (block Jacobi, a truncated band, a border too wide for the exact elimination)
                                 * always iterate to pcg_tolerance. */
 } osfm_ba_options;

@@ -510,16 +510,12 @@ static int match_pairs_impl(osfm_ctx *ctx, const osfm_store *store, const int32_
     return OSFM_OK;
   };
 
-  if (nchunks > 0) {
-    const int rc0 = enqueue_match(0);
-    if (rc0 != OSFM_OK) return rc0;
-  }
+  if (nchunks > 0) OSFM_TRY(enqueue_match(0));
   for (int64_t k = 0; k < nchunks; ++k) {
     ChunkSet &S = sets[k & 1];
     const int64_t p0 = k * cp, np = (n_pairs - p0) < cp ? (n_pairs - p0) : cp;
     if (k + 1 < nchunks) {  // its buffer set was released when chunk k - 1 finished (host synchronised on B)
-      const int rc1 = enqueue_match(k + 1);
-      if (rc1 != OSFM_OK) return rc1;
+      OSFM_TRY(enqueue_match(k + 1));
     }
     OSFM_HIP(hipStreamWaitEvent(stB, S.r0, 0));
     hipEvent_t rb0 = ctx->ev[3], rb1 = ctx->ev[4];

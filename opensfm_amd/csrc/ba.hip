@@ -4282,7 +4282,7 @@ struct Arena {
 
 inline int nblk(long n, int t = TPB) { return (int)std::max<long>(1, (n + t - 1) / t); }  // (never an empty grid: the kernels test their index)
 
-// The environment switches of a solve, read once at the top of ba_solve_impl: mostly cross-checks of the tests; INTEGRATION.md lists the rest.
+// The environment switches of a solve, read once when its Solver is made (Solver::sw): mostly cross-checks of the tests; INTEGRATION.md lists the rest.
 struct BaSwitches {
   bool no_sband = getenv("OSFM_BA_NO_SBAND") != nullptr;            // few shots keep the cyclic reduction, not sband_factor_kernel (test_gpu_ba, test_emu_ba)
   bool check_band = getenv("OSFM_BA_CHECK_BAND") != nullptr;        // the matrix-core band assembly checked against the per-shot kernel (test_gpu_ba)
@@ -4297,18 +4297,156 @@ struct BaSwitches {
   double spin_us = getenv("OSFM_BA_SPIN_US") ? atof(getenv("OSFM_BA_SPIN_US")) : 2000.0;  // ... for this long, then hipStreamSynchronize
 };
 
+// Every BA kernel whose dynamic LDS goes beyond the 64 KB a launch gets without asking, with the bytes it may ask for: set once per device
+// and process, at the top of a solve, whichever of them that solve goes on to launch.
+int ba_kernel_attributes(int device) {
+  static OsfmPerDeviceOnce once;
+  return once.run(device, []() -> int {
+    constexpr int kWholeLds = 160 * 1024;
+    const auto max_lds = [](const void *kernel, int bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+    OSFM_HIP(max_lds((const void *)band_assemble_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)band_assemble_compact_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<1>, 96 * 1024));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<2>, 96 * 1024));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<3>, 96 * 1024));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<4>, 96 * 1024));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<5>, 96 * 1024));
+    OSFM_HIP(max_lds((const void *)band_mfma_kernel<6>, 96 * 1024));
+    for (int q = 2; q <= 10; q++) OSFM_HIP(max_lds((const void *)bcr_level_for(q).fn, kWholeLds));
+    OSFM_HIP(max_lds((const void *)sband_factor_kernel, kWholeLds - 256));  // (+ its two static tables)
+    OSFM_HIP(max_lds((const void *)sband_solve_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)wide_factor_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)dgj_pivot_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)band_cholesky_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)ctri_inverse_kernel, kWholeLds));
+    OSFM_HIP(max_lds((const void *)gen_border_sigma_kernel, kWholeLds - 256));  // (the kernel also has two static words)
+    return OSFM_OK;
+  });
+}
+
+// the matrix-core band assembly for NT 16-row tiles (Dev::bpNT, 1 .. 6)
+typedef void (*band_mfma_fn)(Dev);
+inline band_mfma_fn band_mfma_for(int nt) {
+  static constexpr band_mfma_fn fn[6] = {band_mfma_kernel<1>, band_mfma_kernel<2>, band_mfma_kernel<3>, band_mfma_kernel<4>, band_mfma_kernel<5>, band_mfma_kernel<6>};
+  return fn[nt >= 1 && nt <= 5 ? nt - 1 : 5];
+}
+
+// Everything a solve decides before its first evaluation: which band solver, how it is sized, where the side stream forks.  Filled by the
+// set-up phases of ba_solve_impl and constant from then on; what a failed factorisation changes between iterations are Solver's use_* flags.
+struct SolvePlan {
+  // ---- what the problem is ----
+  int nbord = 0;                              // border unknowns behind the 6 S of the band
+  int bw_true = 0;                            // block half-bandwidth of the shot-shot coupling (track_width_kernel)
+  int track_repeats_shot = 0;                 // some track has two observations in one shot
+  int *bp_keys = nullptr, *bp_pts = nullptr;  // (device) the points in the order of the first shot of their track, for band_mfma_kernel; bp_pts null: more points than observations
+  bool border_ok = true;                      // exact camera border: every camera free (generic mode: the border holds free blocks only)
+  bool all_cams_fixed = false;                // local / pose-only bundle adjustment
+  // ---- the band and its assembly ----
+  bool wide = false;                          // exact band wider than the LDS clusters hold ...
+  bool dense_cr = false;                      // ... by cyclic reduction over dense clusters (else the block LDL^T chain)
+  bool win_band = false;                      // assembled on the matrix cores (band_mfma_kernel), else per shot with LDS atomics
+  int win_grid = 0;
+  size_t win_lds = 0;
+  int band_slice = 0, band_copies = 0;        // per-shot assembly: band columns per launch, private copies of the LDS accumulators
+  int bslot_n = 0, bslot_copies = 1;          // band_assemble_compact_kernel: accumulators over the partners a shot really has
+  // ---- what every LM iteration does ----
+  bool try_bcr = false;                       // the cyclic reduction in LDS clusters (or sband_factor_kernel) factorises the band
+  bool try_border = false;                    // ... with the exact camera border on top
+  bool want_border = false;                   // the side work forms the border's columns
+  bool sband_fuse = false;                    // few shots, constant cameras: the one-workgroup factorisation carries the solve and the start of PCG
+  hipStream_t side2 = nullptr;                // the side stream; null: the iteration has nothing for it (sband_fuse)
+  int fork_at = 0;                            // the side stream starts 0: before the assembly, 1: after it, 2: after the first level of the cyclic reduction
+  bool fork_in_bcr = false;
+  bool exact_expected = false;                // the preconditioner is the reduced matrix: the straight-line iteration is worth trying
+};
+
+// How the trust region judges a step (trust_region_minimizer.cc)
+enum class LmVerdict { Accepted, Rejected, Invalid, ParameterTolerance, FunctionTolerance };
+
+// Host arithmetic only.  dec = scal[8 .. 21] of the iteration's round trip: the candidate's cost [0], the model change [8], the squared norms
+// of the step [9] + [12] and of the parameters [10] + [13]; bad: the linear solve produced no usable step.  Updates radius and decrease_factor.
+inline LmVerdict trust_region_step(const double *dec, bool bad, double cost, const osfm_ba_options *O, int iter, int pcg_iterations, double &radius,
+                                   double &decrease_factor) {
+  const double model_change = dec[8];
+  const double step_sq = dec[9] + dec[12], x_sq = dec[10] + dec[13];
+  if (bad || !(model_change > 0)) {  // HandleInvalidStep + StepIsInvalid
+    radius *= 0.5;
+    return LmVerdict::Invalid;
+  }
+  const double cost_n = dec[0];
+  const double step_norm = std::sqrt(step_sq), x_norm = std::sqrt(x_sq);
+  if (step_norm <= O->parameter_tolerance * (x_norm + O->parameter_tolerance)) return LmVerdict::ParameterTolerance;
+  const double cost_change = cost - cost_n;
+  if (std::fabs(cost_change) <= O->function_tolerance * cost) return LmVerdict::FunctionTolerance;
+  const double rho = cost_change / model_change;
+  if (O->verbose & 1)
+    fprintf(stderr, "[osfm_ba] it %d cost %.9e -> %.9e rho %.3f radius %.3e pcg %d\n", iter, cost, cost_n, rho, radius, pcg_iterations);
+  if (rho > 1e-3) {  // StepAccepted
+    const double t = 2.0 * rho - 1.0;
+    radius = radius / std::fmax(1.0 / 3.0, 1.0 - t * t * t);
+    radius = std::fmin(1e16, radius);
+    decrease_factor = 2.0;
+    return LmVerdict::Accepted;
+  }
+  radius = radius / decrease_factor;  // StepRejected
+  decrease_factor *= 2.0;
+  return LmVerdict::Rejected;
+}
+
 struct Solver {
+  // ---- context, problem image, streams ----
   osfm_ctx *ctx;
   Dev d;
+  BaSwitches sw;
   hipStream_t st;
   int loss;
   double loss_a;
+  // second stream: the camera-border columns and the right-hand side only need the Jacobian and Hhat, so they run underneath the
+  // cyclic-reduction factorisation (a latency chain of ~22 small launches that leaves most CUs idle)
+  hipStream_t st2 = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  int *d_perm = nullptr;       // the point-major order of the caller's observations
+  int *d_status = nullptr;     // status words of the factorisations: [0] cyclic reduction / band Cholesky, [1] border, [2] wide band
+  double *d_reproj = nullptr;  // the reprojection errors, when the caller asks for them
+  // ---- pinned round-trip state ----
   // the LM loop's scalars come back through PINNED host memory (kept by the context): a D2H copy into pageable memory is staged and
   // synchronous in the runtime, ~25 us each; into pinned memory the copies of one round trip are queued back to back
   double *hscal = nullptr;  // 32 doubles
   int *hstat = nullptr;     // 4 ints
   double *hrr = nullptr;    // the blocks' shares of r.r (nbr doubles)
-  int pinned(int nbr, const BaSwitches &sw) {
+  int *hseq = nullptr;
+  int seq = 0, nbr_ = 0;  // nbr_: workgroups of a vector kernel over the reduced unknowns = shares of r.r
+  bool spin = false;
+  double spin_us = 0.0;
+  void *dev_pinned = nullptr;
+  // ---- generic-mode state (kernels: ba_generic.inc) ----
+  int *g_cols = nullptr, *g_col_pos = nullptr;  // generic exact border: the border columns some view holds, and their positions (-1: none)
+  int g_ncols = 0;
+  double *g_wB = nullptr, *g_vpartB = nullptr;  // rows x ncols x NR, views x ncols x KW
+  int gen_uniform_model = -1;  // every camera has this projection type (the evaluation kernel is specialised for the common ones), -1: mixed
+  bool gen_compact = false;    // ... and the rows keep (Xc, wt) instead of their border slots (gen_eval_kernel's COMPACT layout)
+  bool have_bpri = false;  // a prior couples an instance with a free border block (position prior with a free bias, up vector / compass with a free rig camera)
+  std::vector<unsigned char> gen_col_slot;  // (host) the slot of border column j in view v, 255: none
+  // ---- solver-choice flags: what this iteration's factorisation came out as ----
+  bool use_band = false, use_ctri = false, use_bcr = false, use_border = false, use_wide = false;
+  bool use_sband = false;     // the band is factorised by one workgroup (sband_factor_kernel): few shots (fixed at set-up)
+  bool sband_solved = false;  // ... and this iteration's factorisation launch carried the solve of d.b and the start of PCG with it
+  bool z_solved = false;      // M^-1 b went through the border's walk
+  bool joined = true;         // the main stream has waited for this iteration's side work
+  bool have_scale = false;    // the Jacobi scaling is there (first linearisation)
+  double cur_radius = 0.0;    // generic mode: the border rows of the fallback preconditioners are the scaled diagonal at this radius
+  // every camera constant (local / pose-only bundle adjustment): the camera rows have zero scale, zero gradient and zero right-hand side,
+  // so the per-camera sums over the shots (cam_reduce_kernel, 4 launches of ~10 us per LM iteration of a 48-shot problem) are skipped and
+  // camred stays at the zeros it is given at setup
+  bool cams_inert = false;
+  // ---- border buffers ----
+  double *Bc = nullptr, *Wb = nullptr, *SigInv = nullptr, *dots = nullptr;  // border elimination (nb x 6S, nb x 6S, nb x nb, nb x nb)
+  double *yb = nullptr;                                                     // ... r_c - B^T z_s (nb) between the two launches of the long-row path
+  static constexpr int kBorderRhsSplit = 6 * 512;                           // rows of at least this many entries take the two-launch path
+  double *wB = nullptr, *partB = nullptr, *dCm = nullptr;                     // its columns in one pass: w (2 nb per observation), camera partials, C
+  double *sbL = nullptr;                                                    // the one-workgroup band factor, in the band's layout
+
+  int pinned(int nbr) {
     const size_t need = (size_t)(32 + 2 + nbr + 8) * sizeof(double);
     if (ctx->h_pinned_bytes < need) {
       if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -4333,10 +4471,6 @@ struct Solver {
     return OSFM_OK;
   }
   // one host round trip: a (na doubles) -> hscal + ha_off, b (nb ints) -> hstat + hb_off, c (nc doubles) -> hrr
-  int *hseq = nullptr;
-  int seq = 0, nbr_ = 0;
-  bool spin = false;
-  void *dev_pinned = nullptr;
   int fetch(const double *a, int na, int ha_off, const int *b = nullptr, int nb = 0, int hb_off = 0, const double *c = nullptr, int nc = 0) {
     if (!spin) {
       if (na) OSFM_HIP(hipMemcpyAsync(hscal + ha_off, a, (size_t)na * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4361,34 +4495,31 @@ struct Solver {
     }
     return OSFM_OK;
   }
-  double spin_us = 0.0;
 
   void rot(const double *poses) { hipLaunchKernelGGL(shot_rot_kernel, dim3(nblk(d.S, 64)), dim3(64), 0, st, d, poses); }
 
   // ---- generic mode (kernels: ba_generic.inc) ----
-  int *g_cols = nullptr, *g_col_pos = nullptr;  // generic exact border: the border columns some view holds, and their positions (-1: none)
-  int g_ncols = 0;
-  double *g_wB = nullptr, *g_vpartB = nullptr;  // rows x ncols x NR, views x ncols x KW
-  int gen_uniform_model = -1;  // every camera has this projection type (the evaluation kernel is specialised for the common ones), -1: mixed
-  bool gen_compact = false;    // ... and the rows keep (Xc, wt) instead of their border slots (gen_eval_kernel's COMPACT layout)
-  bool have_bpri = false;  // a prior couples an instance with a free border block (position prior with a free bias, up vector / compass with a free rig camera)
-#define OSFM_GEN_KW(NRV, MV, KERNEL, grid, block, stream, ...)                                                \
-  do {                                                                                                        \
-    if (d.g.KW <= 4) hipLaunchKernelGGL((KERNEL<NRV, 4, MV>), grid, block, 0, stream, __VA_ARGS__);            \
-    else if (d.g.KW <= 9) hipLaunchKernelGGL((KERNEL<NRV, 9, MV>), grid, block, 0, stream, __VA_ARGS__);       \
-    else if (d.g.KW <= 16) hipLaunchKernelGGL((KERNEL<NRV, 16, MV>), grid, block, 0, stream, __VA_ARGS__);     \
-    else hipLaunchKernelGGL((KERNEL<NRV, kGenMaxKW, MV>), grid, block, 0, stream, __VA_ARGS__);                \
-  } while (0)
-  // the per-instance kernels recompute their rows (gen_sm_row): specialised, like the evaluation kernel, for the projection type every camera of the
-  // problem has when that is one of the common three
-#define OSFM_GEN_NR_KW(KERNEL, grid, block, stream, ...)                                                                                \
-  do {                                                                                                                                  \
-    if (d.g.NRr == 3) OSFM_GEN_KW(3, -1, KERNEL, grid, block, stream, __VA_ARGS__);                                                       \
-    else if (gen_uniform_model == OSFM_CAMERA_BROWN) OSFM_GEN_KW(2, OSFM_CAMERA_BROWN, KERNEL, grid, block, stream, __VA_ARGS__);         \
-    else if (gen_uniform_model == OSFM_CAMERA_FISHEYE_OPENCV) OSFM_GEN_KW(2, OSFM_CAMERA_FISHEYE_OPENCV, KERNEL, grid, block, stream, __VA_ARGS__); \
-    else if (gen_uniform_model == OSFM_CAMERA_PERSPECTIVE) OSFM_GEN_KW(2, OSFM_CAMERA_PERSPECTIVE, KERNEL, grid, block, stream, __VA_ARGS__); \
-    else OSFM_GEN_KW(2, -1, KERNEL, grid, block, stream, __VA_ARGS__);                                                                    \
-  } while (0)
+  // The generic kernels are specialised for the row width NR (3 with a spherical camera, which is never specialised further) and, with two-row
+  // observations, for the projection type every camera of the problem has when that is one of the common three (MV, -1: mixed).  These two
+  // map the run-time values to the template arguments; the list of specialised models is here and nowhere else.
+  template <class F>
+  void with_gen_model(F &&f) const {
+    using std::integral_constant;
+    if (d.g.NRr == 3) f(integral_constant<int, 3>{}, integral_constant<int, -1>{});
+    else if (gen_uniform_model == OSFM_CAMERA_BROWN) f(integral_constant<int, 2>{}, integral_constant<int, OSFM_CAMERA_BROWN>{});
+    else if (gen_uniform_model == OSFM_CAMERA_FISHEYE_OPENCV) f(integral_constant<int, 2>{}, integral_constant<int, OSFM_CAMERA_FISHEYE_OPENCV>{});
+    else if (gen_uniform_model == OSFM_CAMERA_PERSPECTIVE) f(integral_constant<int, 2>{}, integral_constant<int, OSFM_CAMERA_PERSPECTIVE>{});
+    else f(integral_constant<int, 2>{}, integral_constant<int, -1>{});
+  }
+  // ... and the widest view's border slots (KW) to the slot count the per-instance kernels are compiled for
+  template <class F>
+  void with_gen_kw(F &&f) const {
+    using std::integral_constant;
+    if (d.g.KW <= 4) f(integral_constant<int, 4>{});
+    else if (d.g.KW <= 9) f(integral_constant<int, 9>{});
+    else if (d.g.KW <= 16) f(integral_constant<int, 16>{});
+    else f(integral_constant<int, kGenMaxKW>{});
+  }
   int gen_nprior() const { return d.NC + d.g.NRC + d.S + 4 * d.g.NV; }
   // dynamic LDS of gen_prior_kernel: the workgroup's copy of Cpri and of the border gradient in mode 1, while the border is narrow enough for it
   // (beyond kGenPriorLdsMaxNB the kernel adds to the global arrays directly); modes 0 and 2 use none
@@ -4407,26 +4538,37 @@ struct Solver {
       (void)hipMemsetAsync(d.g.Cpri, 0, (size_t)std::max(1, d.g.NB * d.g.NB) * sizeof(double), st);
       (void)hipMemsetAsync(d.g.gpri, 0, (size_t)d.nred * sizeof(double), st);
     }
-#define OSFM_GEN_EVAL(NRV, MODELV)                                                                                                           \
-  do {                                                                                                                                       \
-    if (jac && gen_compact && MODELV >= 0)                                                                                                   \
-      hipLaunchKernelGGL((gen_eval_kernel<NRV, true, MODELV, (MODELV >= 0)>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a); \
-    else if (jac)                                                                                                                            \
-      hipLaunchKernelGGL((gen_eval_kernel<NRV, true, MODELV>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a);            \
-    else                                                                                                                                     \
-      hipLaunchKernelGGL((gen_eval_kernel<NRV, false, MODELV>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a);           \
-  } while (0)
-    if (d.M > 0) {
-      if (d.g.NRr == 3) OSFM_GEN_EVAL(3, -1);
-      else if (gen_uniform_model == OSFM_CAMERA_BROWN) OSFM_GEN_EVAL(2, OSFM_CAMERA_BROWN);
-      else if (gen_uniform_model == OSFM_CAMERA_FISHEYE_OPENCV) OSFM_GEN_EVAL(2, OSFM_CAMERA_FISHEYE_OPENCV);
-      else if (gen_uniform_model == OSFM_CAMERA_PERSPECTIVE) OSFM_GEN_EVAL(2, OSFM_CAMERA_PERSPECTIVE);
-      else OSFM_GEN_EVAL(2, -1);
-    }
+    if (d.M > 0)
+      with_gen_model([&](auto nr, auto mv) {
+        constexpr int NR = decltype(nr)::value, MV = decltype(mv)::value;
+        if constexpr (MV >= 0) {  // (the COMPACT rows exist for the specialised models, and are written with the Jacobian)
+          if (jac && gen_compact) {
+            hipLaunchKernelGGL((gen_eval_kernel<NR, true, MV, true>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a);
+            return;
+          }
+        }
+        if (jac) hipLaunchKernelGGL((gen_eval_kernel<NR, true, MV>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a);
+        else hipLaunchKernelGGL((gen_eval_kernel<NR, false, MV>), dim3(nb), dim3(TPB), 0, st, d, cam, rcp, poses, pts, loss, loss_a);
+      });
     hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(1024), 0, st, d.partial, (long)(d.M > 0 ? nb : 0), 2, d.scal + 8);
     hipLaunchKernelGGL(gen_prior_kernel, dim3(nblk(gen_nprior(), kGenPriorTPB)), dim3(kGenPriorTPB), gen_prior_lds(jac ? 1 : 0), st, d, cam, bias, rcp, poses, jac ? 1 : 0,
                        (const double *)nullptr, d.scal + 8);
     if (d.g.pt_prior_sigma && d.P > 0) hipLaunchKernelGGL(gen_point_prior_kernel, dim3(nblk(d.P)), dim3(TPB), 0, st, d, pts, 0, d.scal + 8);
+  }
+  // the per-instance kernels recompute their rows (gen_sm_row): specialised like the evaluation kernel
+  void gen_shot_grad() {
+    with_gen_model([&](auto nr, auto mv) {
+      with_gen_kw([&](auto kw) {
+        hipLaunchKernelGGL((gen_shot_grad_kernel<decltype(nr)::value, decltype(kw)::value, decltype(mv)::value>), dim3(d.S), dim3(64), 0, st, d, loss, loss_a);
+      });
+    });
+  }
+  void gen_schur_shot(hipStream_t sq) {
+    with_gen_model([&](auto nr, auto mv) {
+      with_gen_kw([&](auto kw) {
+        hipLaunchKernelGGL((gen_schur_shot_kernel<decltype(nr)::value, decltype(kw)::value, decltype(mv)::value>), dim3(d.S), dim3(64), 0, sq, d);
+      });
+    });
   }
   void gen_gradients() {
     if (d.M > 0) {
@@ -4434,48 +4576,38 @@ struct Solver {
       else hipLaunchKernelGGL(gen_point_grad_kernel<2>, dim3(d.nwg), dim3(kCoopObs), 0, st, d);
     } else if (d.P > 0)
       hipLaunchKernelGGL(gen_point_grad_empty_kernel, dim3(nblk(d.P)), dim3(TPB), 0, st, d);
-    OSFM_GEN_NR_KW(gen_shot_grad_kernel, dim3(d.S), dim3(64), st, d, loss, loss_a);
+    gen_shot_grad();
     if (d.g.NB > 0) {
       hipLaunchKernelGGL(gen_border_reduce_kernel, dim3(d.g.NB), dim3(256), 0, st, d, 2 * d.g.KW, 0, 1);
       hipLaunchKernelGGL(gen_border_reduce_kernel, dim3(d.g.NB), dim3(256), 0, st, d, 2 * d.g.KW, d.g.KW, 2);
     }
   }
-  // pass A over two-row observations, mode 0 (mat-vec) / 1 (right-hand side) / 2 (back-substitution): the COMPACT rows' readers are specialised per projection type
+  // pass A over the observations, mode 0 (mat-vec) / 1 (right-hand side) / 2 (back-substitution): the COMPACT rows' readers are specialised per projection type
   template <int MODE>
-  void gen_schur_point2_mode(hipStream_t sq) {
+  void gen_schur_point_mode(hipStream_t sq) {
     const dim3 grid(d.nwg), block(kCoopObs);
-    if constexpr (MODE != 1) {  // (mode 1, the right-hand side, does not read the border slots)
-      if (gen_compact && gen_uniform_model == OSFM_CAMERA_BROWN) {
-        hipLaunchKernelGGL((gen_schur_point_kernel<2, MODE, OSFM_CAMERA_BROWN, true>), grid, block, 0, sq, d, (const double *)d.y);
-        return;
+    with_gen_model([&](auto nr, auto mv) {
+      constexpr int NR = decltype(nr)::value, MV = decltype(mv)::value;
+      if constexpr (MV >= 0 && MODE != 1) {  // (mode 1, the right-hand side, does not read the border slots)
+        if (gen_compact) {
+          hipLaunchKernelGGL((gen_schur_point_kernel<NR, MODE, MV, true>), grid, block, 0, sq, d, (const double *)d.y);
+          return;
+        }
       }
-      if (gen_compact && gen_uniform_model == OSFM_CAMERA_FISHEYE_OPENCV) {
-        hipLaunchKernelGGL((gen_schur_point_kernel<2, MODE, OSFM_CAMERA_FISHEYE_OPENCV, true>), grid, block, 0, sq, d, (const double *)d.y);
-        return;
-      }
-      if (gen_compact && gen_uniform_model == OSFM_CAMERA_PERSPECTIVE) {
-        hipLaunchKernelGGL((gen_schur_point_kernel<2, MODE, OSFM_CAMERA_PERSPECTIVE, true>), grid, block, 0, sq, d, (const double *)d.y);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((gen_schur_point_kernel<2, MODE>), grid, block, 0, sq, d, (const double *)d.y);
+      hipLaunchKernelGGL((gen_schur_point_kernel<NR, MODE>), grid, block, 0, sq, d, (const double *)d.y);
+    });
   }
-  void gen_schur_point2(int mode, hipStream_t sq) {
-    if (mode == 0) gen_schur_point2_mode<0>(sq);
-    else if (mode == 1) gen_schur_point2_mode<1>(sq);
-    else gen_schur_point2_mode<2>(sq);
+  void gen_schur_point(int mode, hipStream_t sq) {
+    if (mode == 0) gen_schur_point_mode<0>(sq);
+    else if (mode == 1) gen_schur_point_mode<1>(sq);
+    else gen_schur_point_mode<2>(sq);
   }
   // the observation rows' share of J^T (I - Jp Hhat Jp^T) J y (mode 0, y = d.y) or of the right-hand side (mode 1) into zc, on stream sq
   void gen_rows_apply(int mode, hipStream_t sq) {
     if (d.M <= 0) return;
     if (mode == 0 && d.g.KW > 0) hipLaunchKernelGGL(gen_view_gather_kernel, dim3(nblk((long)d.g.NV * d.g.KW)), dim3(TPB), 0, sq, d, (const double *)d.y);
-    if (d.g.NRr == 3) {
-      if (mode == 0) hipLaunchKernelGGL((gen_schur_point_kernel<3, 0>), dim3(d.nwg), dim3(kCoopObs), 0, sq, d, (const double *)d.y);
-      else hipLaunchKernelGGL((gen_schur_point_kernel<3, 1>), dim3(d.nwg), dim3(kCoopObs), 0, sq, d, (const double *)d.y);
-    } else {
-      gen_schur_point2(mode, sq);
-    }
-    OSFM_GEN_NR_KW(gen_schur_shot_kernel, dim3(d.S), dim3(64), sq, d);
+    gen_schur_point(mode, sq);
+    gen_schur_shot(sq);
     if (d.g.NB > 0) hipLaunchKernelGGL(gen_border_reduce_kernel, dim3(d.g.NB), dim3(256), 0, sq, d, 2 * d.g.KW, 0, 0);
   }
   // every column of the border in one pass over the observations (kernels at the end of ba_generic.inc) into Bc / dCm, on stream sq
@@ -4484,6 +4616,7 @@ struct Solver {
     for (int c0 = 0; c0 < g_ncols; c0 += CH)
       hipLaunchKernelGGL((gen_border_shot_kernel<NRV, KWT, CH, MV>), dim3(d.S), dim3(64), 0, sq, d, (const int *)g_cols, g_ncols, c0, (const double *)g_wB, Bc, g_vpartB);
   }
+  // (the ladder over KW stays written out here: each slot count comes with its own number of columns per launch)
   template <int NRV, int MV>
   void gen_border_columns_nr(hipStream_t sq) {
     if (d.M > 0 && g_ncols > 0) {
@@ -4501,11 +4634,7 @@ struct Solver {
     }
   }
   void gen_border_columns(double radius, hipStream_t sq) {
-    if (d.g.NRr == 3) gen_border_columns_nr<3, -1>(sq);
-    else if (gen_uniform_model == OSFM_CAMERA_BROWN) gen_border_columns_nr<2, OSFM_CAMERA_BROWN>(sq);
-    else if (gen_uniform_model == OSFM_CAMERA_FISHEYE_OPENCV) gen_border_columns_nr<2, OSFM_CAMERA_FISHEYE_OPENCV>(sq);
-    else if (gen_uniform_model == OSFM_CAMERA_PERSPECTIVE) gen_border_columns_nr<2, OSFM_CAMERA_PERSPECTIVE>(sq);
-    else gen_border_columns_nr<2, -1>(sq);
+    with_gen_model([&](auto nr, auto mv) { gen_border_columns_nr<decltype(nr)::value, decltype(mv)::value>(sq); });
     const int NB = d.g.NB;
     hipLaunchKernelGGL(gen_border_finish_kernel, dim3(NB * NB + nblk((long)NB * 6 * d.S)), dim3(256), 0, sq, d, (const int *)g_col_pos, std::max(1, g_ncols),
                        (const double *)g_vpartB, Bc, dCm, radius, have_bpri ? 1 : 0);
@@ -4534,10 +4663,7 @@ struct Solver {
   int eval(const double *cams, const double *poses, const double *pts, bool jac, double *cost, double *sumsq) {
     eval_enqueue(cams, poses, pts, jac);
     OSFM_HIP(hipGetLastError());  // a launch the runtime refused (LDS, grid) must not come back as a cost of stale numbers
-    {
-      const int rcf = fetch(d.scal + 8, 2, 0);
-      if (rcf != OSFM_OK) return rcf;
-    }
+    OSFM_TRY(fetch(d.scal + 8, 2, 0));
     *cost = hscal[0];
     if (sumsq) *sumsq = hscal[1];
     return OSFM_OK;
@@ -4549,23 +4675,7 @@ struct Solver {
     if (!cams_inert) hipLaunchKernelGGL(cam_reduce_kernel, dim3(d.NC), dim3(kCamRedT), 0, st, d, 9, (const double *)d.cams);
     else hipLaunchKernelGGL(cam_grad_kernel, dim3(nblk(d.NC, 64)), dim3(64), 0, st, d, d.cams);
   }
-  bool use_band = false, use_ctri = false, use_bcr = false, use_border = false;
-  // every camera constant (local / pose-only bundle adjustment): the camera rows have zero scale, zero gradient and zero right-hand side,
-  // so the per-camera sums over the shots (cam_reduce_kernel, 4 launches of ~10 us per LM iteration of a 48-shot problem) are skipped and
-  // camred stays at the zeros it is given at setup
-  bool cams_inert = false;
-  // second stream: the camera-border columns and the right-hand side only need the Jacobian and Hhat, so they run underneath the
-  // cyclic-reduction factorisation (a latency chain of ~22 small launches that leaves most CUs idle)
-  hipStream_t st2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  double *Bc = nullptr, *Wb = nullptr, *SigInv = nullptr, *dots = nullptr;  // border elimination (nb x 6S, nb x 6S, nb x nb, nb x nb)
-  double *yb = nullptr;                                                     // ... r_c - B^T z_s (nb) between the two launches of the long-row path
-  static constexpr int kBorderRhsSplit = 6 * 512;                           // rows of at least this many entries take the two-launch path
-  double *wB = nullptr, *partB = nullptr, *dCm = nullptr;                     // its columns in one pass: w (2 nb per observation), camera partials, C
   // z_q = A^-1 r_q for nrhs right-hand sides (strides in doubles) in one walk of the levels
-  bool use_sband = false;   // the band is factorised by one workgroup (sband_factor_kernel): few shots
-  bool sband_solved = false;  // ... and this iteration's factorisation launch carried the solve of d.b and the start of PCG with it
-  double *sbL = nullptr;    // ... its factor, in the band's layout
   void bcr_solve_set(const RhsSet &rs) {
     if (use_sband) {
       hipLaunchKernelGGL(sband_solve_kernel, dim3((rs.nrhs + kSbSolveWaves - 1) / kSbSolveWaves), dim3(64 * kSbSolveWaves), sband_solve_lds(d.S, d.bw), st, d,
@@ -4583,7 +4693,6 @@ struct Solver {
     for (int s = st0 / 2; s >= 2; s /= 2) hipLaunchKernelGGL(bcr_up_kernel, dim3(ne(s), q), dim3(64), 0, st, d, s, rs, 0);
     hipLaunchKernelGGL(bcr_up_kernel, dim3(std::max(ne(1), rs.cam_q >= 0 ? (d.NC + 63) / 64 : 0), q), dim3(64), 0, st, d, 1, rs, 1);
   }
-  bool use_wide = false;
   // the same for the wide band: right-hand sides side by side (at most 4 per walk) through L y = b, z = D^-1 y, L^T x = z
   template <int NR>
   void wide_walk(const RhsSet &rs) {
@@ -4646,14 +4755,6 @@ struct Solver {
     const int m = d.qm, N = d.qN;
     const long m2 = (long)m * m;
     const double neg = -1.0, one = 1.0, zero = 0.0;
-    {
-      static OsfmPerDeviceOnce once;
-      const int rca = once.run(ctx->device, []() -> int {
-        OSFM_HIP(hipFuncSetAttribute((const void *)dgj_pivot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return OSFM_OK;
-      });
-      if (rca != OSFM_OK) return rca;
-    }
     hipLaunchKernelGGL(dbcr_build_kernel, dim3((unsigned)((m2 + 255) / 256), (unsigned)N), dim3(256), 0, st, d, d_status);
     const unsigned tl = (unsigned)((m + 31) / 32);
     int cur = 0;
@@ -4662,8 +4763,7 @@ struct Solver {
       const int nR = (N - 1) / (2 * s);          // ... that have a right neighbour (2k + 2) s < N
       const long sk = 2L * s * m2;               // from one cluster of the level to the next, in m x m blocks of one array
       double *Di = d.qD + (long)s * m2, *Ei = d.qE[cur] + (long)s * m2, *Er = d.qE[cur] + 2L * s * m2, *Xi = d.qX + (long)s * 2 * m2;
-      const int rci = dbcr_invert_batch(Di, sk, ne, d_status);
-      if (rci != OSFM_OK) return rci;
+      OSFM_TRY(dbcr_invert_batch(Di, sk, ne, d_status));
       // G_i = D_i^-1 E_i,  H_i = D_i^-1 E_r^T
       gemm_launch({gemm_prob(false, false, m, m, m, one, Di, m, sk, Ei, m, sk, zero, Xi, m, 2 * sk, ne),
                    gemm_prob(false, true, m, m, m, one, Di, m, sk, Er, m, sk, zero, Xi + m2, m, 2 * sk, nR)});
@@ -4676,8 +4776,7 @@ struct Solver {
       dgemm_sb(true, false, m, m, m, neg, Ei, m, sk, Xi, m, 2 * sk, one, d.qD, m, sk, ne);
       cur ^= 1;
     }
-    const int rcr = dbcr_invert_batch(d.qD, m2, 1, d_status);  // the last cluster standing
-    if (rcr != OSFM_OK) return rcr;
+    OSFM_TRY(dbcr_invert_batch(d.qD, m2, 1, d_status));  // the last cluster standing
     OSFM_HIP(hipGetLastError());
     return OSFM_OK;
   }
@@ -4718,7 +4817,6 @@ struct Solver {
     else bcr_solve_set(rs);
   }
   // z = M^-1 r; solved: the exact band solve of r is already in z (it went through the walk of the camera border's columns)
-  double cur_radius = 0.0;  // generic mode: the border rows of the fallback preconditioners are the scaled diagonal at this radius
   void precond(const double *r, double *z, bool solved = false) {
     const RhsSet one{r, 0, z, 0, 1, nullptr, nullptr, -1, d.gen ? -1 : 0};
     if ((use_bcr || use_wide) && use_border) {
@@ -4764,6 +4862,505 @@ struct Solver {
     schur_shot(st);
     hipLaunchKernelGGL(schur_finish_kernel, dim3(matvec_parts()), dim3(TPB), 0, st, d, x, (const double *)d.y, out, radius, 0, cams_inert ? 1 : 0, dot_part);
   }
+
+  // ---- the LM iteration, step by step (lm_loop at the end calls them in this order) ------------------------------------------------------
+  // OSFM_BA_TRACE: a line per phase on stderr, both streams drained -- where a solve stalls
+  int mark(const char *what) {
+    if (!sw.trace) return OSFM_OK;
+    fprintf(stderr, "[osfm_ba trace] %s ...", what);
+    fflush(stderr);
+    OSFM_HIP(hipStreamSynchronize(st));
+    OSFM_HIP(hipStreamSynchronize(st2));
+    OSFM_HIP(hipGetLastError());
+    fprintf(stderr, " done\n");
+    return OSFM_OK;
+  }
+  // after a Jacobian evaluation: gradients, (first time) the Jacobi scaling, the LM diagonal and max |gradient| into scal[10]
+  int prepare_enqueue() {
+    const long nvec = std::max<long>(d.nred, 3L * d.P);
+    gradients();
+    if (!have_scale) {
+      hipLaunchKernelGGL(scale_init_kernel, dim3(nblk(nvec)), dim3(TPB), 0, st, d);
+      have_scale = true;
+    }
+    if (d.gen) OSFM_HIP(hipMemsetAsync(d.scal + 10, 0, sizeof(double), st));  // (the [k1 k2 focal] mode: cleared by prior_cost_kernel, which every evaluation runs)
+    if (nvec <= 65536) {  // small problems: the LM diagonal and max |gradient| in one launch (at configs[4] size the fused kernel was 34 us against 10 + 13)
+      hipLaunchKernelGGL(lm_diag_absmax_kernel, dim3((unsigned)nblk(nvec)), dim3(256), 0, st, d, d.scal + 10);
+    } else {
+      hipLaunchKernelGGL(lm_diag_kernel, dim3(nblk(nvec)), dim3(TPB), 0, st, d);
+      hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, st, d.g_red, (long)d.nred, d.g_pt, 3L * d.P, d.scal + 10);
+    }
+    return OSFM_OK;
+  }
+  // the right-hand side of the reduced system into d.b, on stream sq
+  void rhs_enqueue(double radius, hipStream_t sq) {
+    if (d.gen) {
+      gen_rows_apply(1, sq);
+      hipLaunchKernelGGL(gen_schur_finish_kernel, dim3(nbr_), dim3(TPB), 0, sq, d, (const double *)d.x, (const double *)d.y, d.b, radius, 1, d.M > 0 ? 1 : 0, 0, (double *)nullptr);
+    } else {
+      hipLaunchKernelGGL(schur_point_coop_kernel<1>, dim3(d.nwg), dim3(kCoopObs), 0, sq, d, d.y);
+      schur_shot(sq);
+      hipLaunchKernelGGL(schur_finish_kernel, dim3(matvec_parts()), dim3(TPB), 0, sq, d, (const double *)d.x, (const double *)d.y, d.b, radius, 1, cams_inert ? 1 : 0,
+                         (double *)nullptr);
+    }
+  }
+  int fork_side(hipStream_t side2) {  // the side stream continues from this point of the main stream
+    OSFM_HIP(hipEventRecord(ev_fork, st));
+    OSFM_HIP(hipStreamWaitEvent(side2, ev_fork, 0));
+    return OSFM_OK;
+  }
+  int join() {  // the main stream continues after the side stream's work; as often as a step needs it, the wait is issued once per iteration
+    if (!joined) OSFM_HIP(hipStreamWaitEvent(st, ev_join, 0));
+    joined = true;
+    return OSFM_OK;
+  }
+  // OSFM_BA_CHECK_BAND, the self-check knob of the tests: the per-shot kernel must agree with the matrix-core assembly to rounding
+  int check_band(const SolvePlan &pl, double radius) {
+    const size_t nbd = (size_t)d.S * (d.bw + 1) * 36;
+    std::vector<double> b_win(nbd), b_shot(nbd);
+    OSFM_HIP(hipMemcpyAsync(b_win.data(), d.band, nbd * sizeof(double), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(band_assemble_kernel, dim3(d.S), dim3(TPB), (size_t)(d.bw + 1) * 36 * pl.band_copies * sizeof(double), st, d, radius, pl.band_copies, 0, d.bw + 1);
+    OSFM_HIP(hipMemcpyAsync(b_shot.data(), d.band, nbd * sizeof(double), hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipStreamSynchronize(st));
+    double amax = 0, dmax = 0;
+    for (size_t q = 0; q < nbd; q++) {
+      amax = std::max(amax, std::fabs(b_shot[q]));
+      dmax = std::max(dmax, std::fabs(b_shot[q] - b_win[q]));
+    }
+    OSFM_REQUIRE(dmax <= 1e-10 * amax, OSFM_E_NUMERIC, "band_mfma_kernel differs from band_assemble_kernel: max |diff| %.3e against max |entry| %.3e", dmax, amax);
+    OSFM_HIP(hipMemcpyAsync(d.band, b_win.data(), nbd * sizeof(double), hipMemcpyHostToDevice, st));
+    OSFM_HIP(hipStreamSynchronize(st));
+    return OSFM_OK;
+  }
+  // the band of the reduced matrix at this radius into d.band (d.bw > 0)
+  int assemble_band(const SolvePlan &pl, double radius) {
+    if (pl.win_band) {
+      hipLaunchKernelGGL(band_mfma_for(d.bpNT), dim3(pl.win_grid), dim3(384), pl.win_lds, st, d);
+      hipLaunchKernelGGL(band_finish_kernel, dim3(nblk((long)d.S * (d.bw + 1) * 36)), dim3(TPB), 0, st, d, radius);
+      if (sw.check_band) OSFM_TRY(check_band(pl, radius));
+    } else if (d.bslot) {
+      hipLaunchKernelGGL(band_assemble_compact_kernel, dim3(d.S), dim3(TPB), (size_t)pl.bslot_n * 36 * pl.bslot_copies * sizeof(double) + ((d.bw + 1 + 15) / 16) * 16, st, d,
+                         radius, pl.bslot_copies, pl.bslot_n);
+    } else {
+      for (int lo = 0; lo <= d.bw; lo += pl.band_slice)
+        hipLaunchKernelGGL(band_assemble_kernel, dim3(d.S), dim3(TPB), (size_t)std::min(pl.band_slice, d.bw + 1 - lo) * 36 * pl.band_copies * sizeof(double), st, d,
+                           radius, pl.band_copies, lo, std::min(pl.band_slice, d.bw + 1 - lo));
+    }
+    return OSFM_OK;
+  }
+  // the side stream's work: the camera border's columns and the right-hand side, from the point of the main stream where it is called
+  int side_work(const SolvePlan &pl, double radius, bool fork_here) {
+    const hipStream_t sx = pl.side2 ? pl.side2 : st;
+    if (pl.side2 && fork_here) OSFM_TRY(fork_side(pl.side2));
+    if (pl.want_border && d.gen) {
+      gen_border_columns(radius, sx);
+    } else if (pl.want_border) {  // all nb columns of B (and of the camera block C) in one pass over the observations
+      if (3 * d.NC == 3) {
+        hipLaunchKernelGGL(border_point_kernel<3>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, wB);
+        if (shot_waves() > 1) hipLaunchKernelGGL((border_shot_kernel<3, kShotWavesSmall>), dim3(d.S), dim3(64 * kShotWavesSmall), 0, sx, d, wB, Bc, partB);
+        else hipLaunchKernelGGL((border_shot_kernel<3, 1>), dim3(d.S), dim3(64), 0, sx, d, wB, Bc, partB);
+        hipLaunchKernelGGL(border_cam_kernel<3>, dim3(d.NC), dim3(TPB), 0, sx, d, partB, dCm, radius);
+      } else {
+        hipLaunchKernelGGL(border_point_kernel<6>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, wB);
+        if (shot_waves() > 1) hipLaunchKernelGGL((border_shot_kernel<6, kShotWavesSmall>), dim3(d.S), dim3(64 * kShotWavesSmall), 0, sx, d, wB, Bc, partB);
+        else hipLaunchKernelGGL((border_shot_kernel<6, 1>), dim3(d.S), dim3(64), 0, sx, d, wB, Bc, partB);
+        hipLaunchKernelGGL(border_cam_kernel<6>, dim3(d.NC), dim3(TPB), 0, sx, d, partB, dCm, radius);
+      }
+    }
+    if (!pl.sband_fuse) rhs_enqueue(radius, sx);  // (sband_fuse: done already, on the main stream)
+    if (pl.side2) OSFM_HIP(hipEventRecord(ev_join, pl.side2));
+    return OSFM_OK;
+  }
+  // Sigma^-1 = (C - B^T W)^-1 on the device; its status joins the factorisation's
+  void border_sigma(int nb, int n6) {
+    hipLaunchKernelGGL(border_dots_kernel, dim3(nb * nb), dim3(TPB), 0, st, Bc, Wb, nb, n6, dots);
+    if (nb <= 6)
+      hipLaunchKernelGGL(border_sigma_kernel, dim3(1), dim3(64), 0, st, dCm, dots, SigInv, nb, d_status + 1);
+    else
+      hipLaunchKernelGGL(gen_border_sigma_kernel, dim3(1), dim3(256), (size_t)nb * 2 * nb * sizeof(double), st, (const double *)dCm, (const double *)dots, SigInv, nb, d_status + 1);
+  }
+  // the wide band: cyclic reduction over dense clusters or the block LDL^T chain, and the exact border on top
+  int factorise_wide(const SolvePlan &pl) {
+    if (pl.dense_cr) {  // cyclic reduction over dense clusters: log2(S / bw) levels of batched dense operations
+      OSFM_TRY(dbcr_factor(d_status));
+    } else {  // direct block LDL^T of the exact band: one launch per block column
+      hipLaunchKernelGGL(wide_tiles_kernel, dim3(d.wNB, d.wWb + 1), dim3(256), 0, st, d, d_status);
+      const int ntile = d.wWb * (d.wWb + 1) / 2;
+      for (int J = 0; J < d.wNB; J++) {
+        const int left = std::min(d.wWb, d.wNB - 1 - J);  // rows of the window that exist below block column J
+        hipLaunchKernelGGL(wide_factor_kernel, dim3(1 + (left == d.wWb ? ntile : left * (left + 1) / 2)), dim3(256), (size_t)2 * kWB * kWLd * sizeof(double), st, d, J, d_status);
+      }
+    }
+    use_wide = true;
+    if (pl.try_border) {
+      const int nb = pl.nbord, n6 = 6 * d.S;
+      OSFM_TRY(join());
+      wide_solve_set(RhsSet{Bc, n6, Wb, n6, nb + 1, d.b, d.z, nb, d.gen ? -1 : nb});  // the border's columns and the solve's own right-hand side
+      z_solved = true;
+      border_sigma(nb, n6);
+      use_border = true;
+    }
+    return OSFM_OK;
+  }
+  // the narrow band: one workgroup (few shots) or the cyclic reduction in LDS clusters, and the exact border on top.  With fork_in_bcr the
+  // side work starts from inside: beside sband_factor_kernel, or behind the first level of the cyclic reduction.
+  int factorise_bcr(const SolvePlan &pl, double radius) {
+    const int N = d.ncl;
+    if (use_sband) {  // one workgroup factorises the band; the side stream's work runs beside it
+      if (pl.fork_in_bcr) OSFM_TRY(side_work(pl, radius, true));
+      if (pl.sband_fuse) {  // the right-hand side must be there: the side stream was forked before the assembly
+        OSFM_TRY(join());
+        hipLaunchKernelGGL(sband_factor_kernel, dim3(1), dim3(kSbThreads), sband_factor_lds(d.S, d.bw), st, d, sbL, d_status, RhsSet{d.b, 0, d.z, 0, 1, nullptr, nullptr, -1, 0},
+                           SbFuse{1, radius, d.x, d.r, d.p, d.y, d.scal + 0, d.scal + 4, d.sc_red});
+        sband_solved = true;
+      } else {
+        hipLaunchKernelGGL(sband_factor_kernel, dim3(1), dim3(kSbThreads), sband_factor_lds(d.S, d.bw), st, d, sbL, d_status, RhsSet{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, -1, -1},
+                           SbFuse{0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
+      }
+    } else {
+      hipLaunchKernelGGL(bcr_build_kernel, dim3(N), dim3(256), 0, st, d, d_status);
+      const BcrLaunch lv = bcr_level_for(d.cs);
+      for (int stq = 1; stq < N; stq *= 2) {
+        hipLaunchKernelGGL(lv.fn, dim3((N + 2 * stq - 1) / (2 * stq)), dim3(lv.threads), lv.lds_bytes, st, d, stq, 0, d_status);
+        if (stq == 1 && pl.fork_in_bcr) OSFM_TRY(side_work(pl, radius, true));
+      }
+      hipLaunchKernelGGL(lv.fn, dim3(1), dim3(lv.threads), lv.lds_bytes, st, d, 1, 1, d_status);
+    }
+    use_bcr = true;
+    if (pl.try_border) {  // exact camera border (few cameras, all free): B = S e_j restricted to the shot rows, W = A^-1 B
+      const int nb = pl.nbord, n6 = 6 * d.S;
+      // the columns of B and C were formed on the side stream; W = A^-1 B for all of them in one walk of the levels
+      OSFM_TRY(join());
+      for (int q0 = 0; q0 < nb + 1; q0 += kWalkRhs) {  // (the work vectors of a walk hold kWalkRhs right-hand sides)
+        const int cnt = std::min(kWalkRhs, nb + 1 - q0), qx = (nb >= q0 && nb < q0 + cnt) ? nb - q0 : -1;
+        bcr_solve_set(RhsSet{Bc + (long)q0 * n6, n6, Wb + (long)q0 * n6, n6, cnt, d.b, d.z, qx, d.gen ? -1 : qx});  // the border's columns and the solve's own right-hand side
+      }
+      z_solved = true;
+      border_sigma(nb, n6);
+      use_border = true;
+    }
+    return OSFM_OK;
+  }
+  // sequential banded block Cholesky (truncated band, or the cyclic reduction said no)
+  int fallback_band() {
+    const int R = d.bw + 1;
+    hipLaunchKernelGGL(band_cholesky_kernel, dim3(1), dim3(64), (size_t)((kMaxBw + 1) * R * 36 + (kMaxBw + 1) * 36 + 72) * sizeof(double), st, d, d_status);
+    hstat[3] = 1;
+    OSFM_HIP(hipMemcpyAsync(hstat + 3, d_status, sizeof(int), hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipStreamSynchronize(st));
+    use_band = (hstat[3] == 0);  // a truncated band may lose positive definiteness: fall back to block Jacobi
+    if (use_band && d.ncl > 0) {
+      const size_t n2 = (size_t)d.ncd * d.ncd;
+      OSFM_HIP(hipMemsetAsync(d.cD, 0, (size_t)d.ncl * n2 * sizeof(double), st));
+      OSFM_HIP(hipMemsetAsync(d.cW, 0, (size_t)(d.ncl + 1) * n2 * sizeof(double), st));
+      OSFM_HIP(hipMemsetAsync(d.cWt, 0, (size_t)(d.ncl + 1) * n2 * sizeof(double), st));
+      hipLaunchKernelGGL(ctri_pad_kernel, dim3(1), dim3(64), 0, st, d);
+      hipLaunchKernelGGL(ctri_scatterL_kernel, dim3(d.S), dim3(TPB), 0, st, d);
+      hipLaunchKernelGGL(ctri_inverse_kernel, dim3(d.ncl), dim3(64), 2 * n2 * sizeof(double), st, d);
+      use_ctri = true;
+    }
+    return OSFM_OK;
+  }
+  // One LM iteration's linear system, as far as the host can go without an answer from the device: Hhat, the band, the side work (border
+  // columns, right-hand side), the factorisation with the border on top.
+  // The cyclic reduction (and the camera border on top of it) is issued without asking whether it succeeded: its status words come
+  // back with the first scalars of PCG -- one host round trip for the factorisation, the border and the start of the solve.  When a
+  // status says no (a pivot block that is not positive definite, a singular border) the fallbacks are issued and PCG starts again.
+  int build_and_factorise(const SolvePlan &pl, double radius) {
+    hipLaunchKernelGGL(point_hhat_kernel, dim3(nblk(d.P)), dim3(TPB), 0, st, d, radius);
+    use_band = use_ctri = use_bcr = use_wide = use_border = false;
+    sband_solved = z_solved = false;
+    joined = pl.side2 == nullptr;
+    cur_radius = radius;
+    // ---- fork: camera-border columns (if this problem uses them) and the right-hand side only need the Jacobian and Hhat: they run on
+    //      the side stream next to the band assembly (a gather that leaves HBM bandwidth unused), so that the cyclic-reduction levels
+    //      -- workgroups that need a whole CU's LDS -- find the CUs free afterwards ----
+    // where the side stream starts (SolvePlan::fork_at): the per-shot assembly (LDS atomics) leaves HBM idle, so the border's passes run beside it; the
+    // matrix-core assembly fills the CUs (four workgroups of 39 KB LDS each), and the side stream starts after it, beside the cyclic
+    // reduction's levels -- one 117 KB workgroup per CU, which leaves the CU room for a border workgroup
+    // (round 6: with the matrix-core assembly the side stream starts behind the FIRST LEVEL of the cyclic reduction -- its 278 workgroups of 117 KB
+    //  LDS need every CU twice over, the later levels leave half of them and more to the border's kernels: 3.13 -> 3.09 ms per LM iteration at
+    //  configs[4], profiles/r06_ba_variants.json; everything on one stream: 3.31)
+    // few shots, constant cameras (sband_fuse): the one-workgroup factorisation carries the solve, so the right-hand side goes in front of it, on the
+    // main stream -- three launches of ~17 us in all, in front of the assembly: a fork and a join cost as much in event latencies
+    if (pl.sband_fuse) rhs_enqueue(radius, st);
+    if (pl.side2 && pl.fork_at == 0) OSFM_TRY(fork_side(pl.side2));
+    if (d.bw > 0) OSFM_TRY(assemble_band(pl, radius));
+    OSFM_TRY(mark("band assembly"));
+    if (!pl.fork_in_bcr) OSFM_TRY(side_work(pl, radius, pl.fork_at >= 1));
+    OSFM_TRY(mark("side work (border columns, right-hand side)"));
+    if (pl.wide) OSFM_TRY(factorise_wide(pl));
+    if (pl.try_bcr) OSFM_TRY(factorise_bcr(pl, radius));
+    if (d.bw > 0 && !pl.try_bcr && !pl.wide) OSFM_TRY(fallback_band());
+    OSFM_TRY(join());  // the right-hand side (and its use of part / camred) is complete
+    OSFM_TRY(mark("factorisation + border solve"));
+    hstat[0] = hstat[1] = hstat[2] = 0;
+    return OSFM_OK;
+  }
+  // the preconditioner's blocks, z = M^-1 b and the start of PCG (x = 0, r = b, p = z, y = sc p; b . b into scal[4])
+  void start_pcg_enqueue(const SolvePlan &pl, double radius) {
+    // block-Jacobi blocks (6x6 per shot, 3x3 per camera): the fallback preconditioner, and the camera rows of the band
+    // preconditioners -- not needed when the cyclic reduction came out with the exact camera border
+    if (d.gen) {
+      if (!(use_bcr || use_wide || use_ctri || use_band)) {
+        if (d.g.NRr == 3) hipLaunchKernelGGL(gen_precond_shot_kernel<3>, dim3(d.S), dim3(64), 0, st, d, radius);
+        else hipLaunchKernelGGL(gen_precond_shot_kernel<2>, dim3(d.S), dim3(64), 0, st, d, radius);
+      }
+    } else if (use_bcr && use_sband && !use_border && pl.all_cams_fixed && !z_solved) {
+      // ... and with the one-workgroup band solve the camera blocks, the solve and the start of PCG are ONE launch (three until round 6) --
+      // or none: the factorisation's launch has done it all
+      if (sband_solved) {
+        sband_solved = false;
+        return;
+      }
+      hipLaunchKernelGGL(sband_solve_kernel, dim3(1), dim3(64 * kSbSolveWaves), sband_solve_lds(d.S, d.bw), st, d, (const double *)sbL,
+                         RhsSet{d.b, 0, d.z, 0, 1, nullptr, nullptr, -1, 0}, SbFuse{1, radius, d.x, d.r, d.p, d.y, d.scal + 0, d.scal + 4, d.sc_red});
+      return;
+    } else if ((use_bcr || use_wide) && pl.all_cams_fixed) {
+      // local / pose-only bundle adjustment: the band is the whole preconditioner and the camera rows are inert (zero scale, zero right-hand
+      // side) -- their 3 x 3 blocks are the LM diagonal alone; the per-shot Schur blocks (63 us per LM iteration on a 48-shot problem) are not needed
+      hipLaunchKernelGGL(precond_cam_kernel, dim3(nblk(d.NC, 64)), dim3(64), 0, st, d, radius);  // (camred: zeros since setup)
+    } else if (!((use_bcr || use_wide) && use_border)) {
+      hipLaunchKernelGGL(precond_shot_kernel, dim3(d.S), dim3(64), 0, st, d, radius);
+      hipLaunchKernelGGL(cam_reduce_kernel, dim3(d.NC), dim3(kCamRedT), 0, st, d, 6, (const double *)nullptr);
+      hipLaunchKernelGGL(precond_cam_kernel, dim3(nblk(d.NC, 64)), dim3(64), 0, st, d, radius);
+    }
+    precond(d.b, d.z, z_solved);
+    z_solved = false;
+    hipLaunchKernelGGL(pcg_init_kernel, dim3(1), dim3(1024), 0, st, d.b, d.z, d.x, d.r, d.p, d.nred, d.scal + 0, d.scal + 4, (const double *)d.sc_red, d.y);  // x = 0, r = b, p = z, y = sc p
+  }
+  // ... with the round trip that brings the factorisations' status words and the first scalars
+  int start_pcg(const SolvePlan &pl, double radius) {
+    start_pcg_enqueue(pl, radius);
+    return fetch(d.scal, 5, 0, d_status, (pl.try_bcr || pl.wide) ? 3 : 0, 0);
+  }
+  bool status_failed(const SolvePlan &pl) const { return (pl.try_bcr && hstat[0] != 0) || (use_wide && hstat[2] != 0) || (use_border && hstat[1] != 0); }
+  // one CG iteration's first half: the mat-vec and x += alpha p, r -= alpha Ap (r . r shares into rrp)
+  void pcg_half(double radius, int rz_cur, bool leave_y = false) {  // leave_y: y = sc x behind the step (the straight-line iteration goes on to the back-substitution)
+    matvec(d.p, d.Ap, radius, true, d.dotp);
+    hipLaunchKernelGGL(pcg_step1_kernel, dim3(nbr_), dim3(TPB), 0, st, d.x, d.r, (const double *)d.p, (const double *)d.Ap, d.nred, (const double *)(d.scal + rz_cur),
+                       (const double *)d.dotp, matvec_parts(), d.scal + 1, d.rrp, (const double *)d.sc_red, leave_y ? d.y : (double *)nullptr);
+  }
+  double residual_sq() const {  // r . r from the shares of the last round trip
+    double rr = 0.0;
+    for (int q = 0; q < nbr_; q++) rr += hrr[(size_t)q];
+    return rr;
+  }
+  // PCG from the started state to convergence; *k: its iterations (0: none run), *bad: NaN on the way
+  int pcg(const osfm_ba_options *O, double radius, int *k, bool *bad) {
+    const double bb = hscal[4];
+    *bad = !(bb == bb) || std::isinf(bb);
+    if (*bad || !(bb > 0)) return OSFM_OK;
+    const double tol2 = O->pcg_tolerance * O->pcg_tolerance * bb;
+    // the preconditioner is the reduced matrix itself: the first iterate is a direct solve (see osfm_ba_options_default)
+    const bool exact_precond = (use_bcr || use_wide) && (use_border || (d.gen ? d.g.NB == 0 : cams_inert));
+    const double tol2_first = exact_precond ? std::max(tol2, O->pcg_direct_tolerance * O->pcg_direct_tolerance * bb) : tol2;
+    const int kmax = O->pcg_max_iterations > 0 ? O->pcg_max_iterations : 1000;
+    // r.z lives in scal[0] and scal[2] alternately (rz_cur: the current one); p . Ap is added up from the mat-vec's shares by the step kernel
+    int rz_cur = 0, rz_nxt = 2;
+    for (*k = 1; *k <= kmax; (*k)++) {
+      pcg_half(radius, rz_cur);
+      // the convergence test comes before the preconditioner is applied to the new residual: the last iteration of a solve does not
+      // pay for a walk of the cyclic reduction whose result nobody reads
+      // (an exact band -- with the camera border on top, or with constant cameras as in local bundle adjustment -- makes the
+      // preconditioner the matrix itself: CG is done after one or two iterations, so the first two are polled)
+      if ((*k & 3) == 0 || *k == kmax || ((use_bcr || use_wide) && *k <= 2)) {
+        OSFM_TRY(fetch(nullptr, 0, 0, nullptr, 0, 0, d.rrp, nbr_));
+        const double rr = residual_sq();
+        if (!(rr == rr)) {
+          *bad = true;
+          break;
+        }
+        if (rr <= (*k == 1 ? tol2_first : tol2)) break;
+      }
+      precond(d.r, d.z);
+      hipLaunchKernelGGL(dot2_kernel, dim3(1), dim3(1024), 0, st, d.r, d.z, (const double *)nullptr, (const double *)nullptr, d.nred, d.scal + rz_nxt, d.scal + 3);
+      hipLaunchKernelGGL(pcg_step2_kernel, dim3(nbr_), dim3(TPB), 0, st, d.p, (const double *)d.z, d.nred, (const double *)(d.scal + rz_cur), (const double *)(d.scal + rz_nxt),
+                         (const double *)d.sc_red, d.y);
+      std::swap(rz_cur, rz_nxt);
+    }
+    return OSFM_OK;
+  }
+  void swap_blocks() {  // the current point and the candidate change places
+    std::swap(d.cams, d.cams_n);
+    std::swap(d.poses, d.poses_n);
+    std::swap(d.pts, d.pts_n);
+    if (d.gen) {
+      std::swap(d.g.cam, d.g.cam_n);
+      std::swap(d.g.bias, d.g.bias_n);
+      std::swap(d.g.rc, d.g.rc_n);
+    }
+  }
+  // A rejected or invalid step, or a failed straight-line iteration: the blocks go back and the old point is linearised again by the same
+  // kernels on the same inputs.  With the [k1 k2 focal] kernels that gives the bits the device held before; in generic mode the prior blocks
+  // and gradients are accumulated with floating-point atomics, so they come back equal up to the order of accumulation -- a difference that is
+  // accepted.  The factorisation, the border and the right-hand side of the iteration are not touched.
+  int relinearise_old_point() {
+    swap_blocks();
+    eval_enqueue(d.cams, d.poses, d.pts, true);
+    return prepare_enqueue();  // (nothing to read: cost, sum of squares and max |gradient| of this point are on the host already)
+  }
+  // Back-substitution, model change, candidate -- and the candidate is LINEARISED before the host has seen the model change (round 6;
+  // rounds 2-5 evaluated its cost alone here and, once the host had accepted the step, came back for the Jacobian): the blocks change
+  // places, the evaluation with Jacobian rows, the gradients, the LM diagonal and max |gradient| are queued behind the back-substitution,
+  // and ONE round trip brings the model change, the step's norms, the candidate's cost and its gradient norm.  An accepted step -- nearly
+  // every step of a converging problem -- has then cost one evaluation instead of two (0.09 ms at configs[4]) and one round trip instead
+  // of two; a rejected or invalid step puts the blocks back and linearises the old point again (relinearise_old_point).
+  int candidate_enqueue(bool y_ready = false) {
+    const int S = d.S, NP = d.P;
+    if (!y_ready) hipLaunchKernelGGL(scale_vec_kernel, dim3(nbr_), dim3(TPB), 0, st, d.sc_red, d.x, d.y, d.nred);
+    if (d.gen) {
+      if (d.M > 0 && d.g.KW > 0) hipLaunchKernelGGL(gen_view_gather_kernel, dim3(nblk((long)d.g.NV * d.g.KW)), dim3(TPB), 0, st, d, (const double *)d.y);
+      gen_schur_point(2, st);
+      hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(1024), 0, st, d.partial, (long)d.nwg, 1, d.scal + 16);  // the model change's observation part
+      hipLaunchKernelGGL(gen_candidate_kernel, dim3(1), dim3(1024), 0, st, d, (const double *)d.y, d.scal + 16);
+      hipLaunchKernelGGL(gen_prior_kernel, dim3(nblk(gen_nprior(), kGenPriorTPB)), dim3(kGenPriorTPB), gen_prior_lds(2), st, d, (const double *)d.g.cam, (const double *)d.g.bias,
+                         (const double *)d.g.rc, (const double *)d.poses, 2, (const double *)d.y, d.scal + 16);
+      if (d.g.pt_prior_sigma && NP > 0) hipLaunchKernelGGL(gen_point_prior_kernel, dim3(nblk(NP)), dim3(TPB), 0, st, d, (const double *)d.pts, 2, d.scal + 16);
+      hipLaunchKernelGGL(candidate_points_kernel, dim3(nblk(3L * NP)), dim3(TPB), 0, st, d, d.partial);
+      hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(1024), 0, st, d.partial, (long)nblk(3L * NP), 2, d.scal + 20);
+    } else {
+      hipLaunchKernelGGL(schur_point_coop_kernel<2>, dim3(d.nwg), dim3(kCoopObs), 0, st, d, d.y);
+      // the points' candidate first (its shares in partial2), then the cameras' and shots' with both sums and the candidate's rotation blocks
+      hipLaunchKernelGGL(candidate_points_kernel, dim3(nblk(3L * NP)), dim3(TPB), 0, st, d, d.partial2);
+      hipLaunchKernelGGL(candidate_kernel, dim3(1), dim3(1024), 0, st, d, (const double *)d.y, (const double *)d.partial, (long)d.nwg, d.scal + 16,
+                         (const double *)d.partial2, (long)nblk(3L * NP), d.scal + 20, S <= 1024 ? 1 : 0);
+    }
+    swap_blocks();
+    eval_enqueue(d.cams, d.poses, d.pts, true, !d.gen && S <= 1024);
+    return prepare_enqueue();
+  }
+  // ---- the straight-line iteration (round 6) ----
+  // With the exact band and the exact border (or constant cameras) the preconditioner is the reduced matrix: CG is one mat-vec, and nothing
+  // the host learns on the way -- the factorisation's status words, |b|, the residual after the first iterate -- changes what is launched
+  // next, except in the rare failure.  So everything is queued back to back: the start of PCG, its first iteration, the back-substitution,
+  // the candidate and its linearisation; ONE round trip brings the status words, the PCG scalars, the shares of r . r, the model change
+  // and the candidate's cost (hscal[8 .. 21] -- the careful path leaves them in hscal[0 .. 13]).  When a status word or the residual says
+  // no (*done stays false), the blocks go back, the old point is linearised again and the caller redoes the iteration on the careful path
+  // (which also keeps the fallbacks): the factorisation, the border and the right-hand side stand, and the status words are read again there.
+  // Three round trips per LM iteration become one (OSFM_BA_NO_FAST keeps the careful path: the cross-check of the tests).
+  int straight_line_step(const SolvePlan &pl, const osfm_ba_options *O, double radius, bool forced_failure, bool *done) {
+    start_pcg_enqueue(pl, radius);
+    pcg_half(radius, 0, true);
+    OSFM_TRY(candidate_enqueue(true));
+    OSFM_TRY(fetch(d.scal, 22, 0, d_status, 3, 0, d.rrp, nbr_));
+    const double bb1 = hscal[4], rr = residual_sq();
+    const double tol_first = std::max(O->pcg_tolerance, O->pcg_direct_tolerance);
+    *done = !forced_failure && !status_failed(pl) && bb1 == bb1 && !std::isinf(bb1) && bb1 > 0 && rr == rr && rr <= tol_first * tol_first * bb1;
+    if (!*done) OSFM_TRY(relinearise_old_point());
+    return OSFM_OK;
+  }
+  // ---- the careful path: a round trip after the start of PCG (status words: the fallbacks), PCG polled for convergence, then the candidate;
+  //      its scalars arrive in hscal[0 .. 13] ----
+  int careful_step(const SolvePlan &pl, const osfm_ba_options *O, double radius, int iter, int *k, bool *bad, int64_t *pcg_total) {
+    OSFM_TRY(start_pcg(pl, radius));
+    if (status_failed(pl)) {
+      if (pl.try_bcr && hstat[0] != 0) {
+        use_bcr = false;
+        use_border = false;
+        OSFM_TRY(fallback_band());
+      } else if (use_wide && hstat[2] != 0) {  // a pivot block of the wide band is not positive definite: block Jacobi
+        use_wide = false;
+        use_border = false;
+      } else {
+        use_border = false;
+      }
+      OSFM_TRY(start_pcg(pl, radius));
+    }
+    OSFM_TRY(pcg(O, radius, k, bad));
+    *pcg_total += *k;
+    OSFM_TRY(mark("pcg"));
+    if (sw.trace) fprintf(stderr, "[osfm_ba trace] iteration %d: %d pcg iterations, status %d %d %d, band %d bcr %d (one workgroup: %d) wide %d dense %d border %d\n", iter, *k, hstat[0], hstat[1],
+                       hstat[2], (int)use_band, (int)use_bcr, (int)(use_bcr && use_sband), (int)use_wide, (int)(use_wide && pl.dense_cr), (int)use_border);
+    OSFM_TRY(candidate_enqueue());
+    return fetch(d.scal + 8, 14, 0);  // scal[8..21]
+  }
+  // The Levenberg-Marquardt loop (ceres' trust-region minimizer) from the linearised first point.  *cost / *sumsq: the first evaluation's on
+  // entry, the last accepted point's on return; *radius: the trust region on return.  Writes the report's iteration counts, cost history and termination.
+  int lm_loop(const SolvePlan &pl, const osfm_ba_options *O, osfm_ba_report *Rp, double *cost_io, double *sumsq_io, double *radius_io) {
+    double cost = *cost_io, sumsq = *sumsq_io;
+    double radius = O->initial_radius > 0 ? O->initial_radius : 1e4;
+    double decrease_factor = 2.0;
+    bool fast_ok = !sw.no_fast;  // the straight-line iteration is tried (until it fails once in this solve)
+    int n_invalid = 0, iter = 0;
+    double lin_seconds = 0;
+    Rp->termination = 0;
+    OSFM_TRY(prepare_enqueue());
+    OSFM_TRY(fetch(d.scal + 10, 1, 0));
+    double gmax = hscal[0];
+    for (;;) {
+      if (iter >= O->max_iterations) { Rp->termination = 0; break; }
+      if (gmax <= O->gradient_tolerance) { Rp->termination = 2; break; }
+      if (radius < 1e-32) { Rp->termination = 4; break; }
+      iter++;
+      OSFM_TRY(mark("gradients / scaling"));
+      if (iter < 256) Rp->cost_history[iter] = cost;  // every exit below (tolerances, invalid step) leaves the slot of this iteration defined
+      const auto t_lin = std::chrono::steady_clock::now();
+      // ---- linear solve: PCG on the implicit Schur complement; then the candidate, linearised ----
+      OSFM_TRY(build_and_factorise(pl, radius));
+      bool bad = false, fast_done = false;
+      int k = 0;
+      const double *dec = hscal;  // scal[8 .. 21] of the iteration's last round trip
+      if (pl.exact_expected && fast_ok && !sw.trace) {
+        // (sw.fast_fail_at, the test knob OSFM_BA_FAST_FAIL_AT: the way back to the careful path, exercised on purpose)
+        OSFM_TRY(straight_line_step(pl, O, radius, sw.fast_fail_at == iter, &fast_done));
+        if (fast_done) {
+          k = 1;
+          Rp->pcg_iterations_total += 1;
+          dec = hscal + 8;
+        } else {
+          fast_ok = false;  // after one failure a solve stays on the careful path
+        }
+      }
+      if (!fast_done) OSFM_TRY(careful_step(pl, O, radius, iter, &k, &bad, &Rp->pcg_iterations_total));
+      lin_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_lin).count();
+      // ---- the trust region ----
+      const LmVerdict verdict = trust_region_step(dec, bad, cost, O, iter, k, radius, decrease_factor);
+      if (verdict == LmVerdict::Invalid) {
+        OSFM_TRY(relinearise_old_point());
+        if (++n_invalid >= 5) { Rp->termination = -1; break; }
+        continue;
+      }
+      n_invalid = 0;
+      if (verdict == LmVerdict::ParameterTolerance || verdict == LmVerdict::FunctionTolerance) {
+        Rp->termination = verdict == LmVerdict::ParameterTolerance ? 3 : 1;
+        swap_blocks();  // the step is not taken (the rows and gradients on the device are the candidate's: nothing reads them after the loop)
+        break;
+      }
+      if (verdict == LmVerdict::Accepted) {  // the blocks are in place and the new point is linearised
+        Rp->successful_steps++;
+        cost = dec[0];
+        sumsq = dec[1];
+        gmax = dec[2];
+      } else {
+        OSFM_TRY(relinearise_old_point());
+      }
+      if (iter < 256) Rp->cost_history[iter] = cost;
+    }
+    Rp->iterations = iter;
+    Rp->final_cost = cost;
+    Rp->seconds_linear_solver = lin_seconds;
+    *cost_io = cost;
+    *sumsq_io = sumsq;
+    *radius_io = radius;
+    return OSFM_OK;
+  }
+  // mat-vec timing sample (HIP events on the solver stream), for the roofline of the dominant kernel: ten extra mat-vecs, only when the
+  // caller asks (OSFM_BA_TIME_MATVEC in options->verbose: the bench does) -- they were 3.9 ms of every configs[4] call's tear-down and as
+  // much as a whole LM iteration of a local bundle adjustment
+  int time_matvec(double radius, osfm_ba_report *Rp) {
+    const int reps = 10;
+    hipLaunchKernelGGL(point_hhat_kernel, dim3(nblk(d.P)), dim3(TPB), 0, st, d, radius);
+    OSFM_HIP(hipEventRecord(ctx->ev[6], st));
+    for (int i = 0; i < reps; i++) matvec(d.p, d.Ap, radius);
+    OSFM_HIP(hipEventRecord(ctx->ev[7], st));
+    OSFM_HIP(hipStreamSynchronize(st));
+    float ms = 0.f;
+    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
+    Rp->ms_matvec_total = ms;
+    Rp->matvec_calls = reps;
+    return OSFM_OK;
+  }
 };
 
 }  // namespace
@@ -4784,7 +5381,7 @@ extern "C" void osfm_ba_options_default(osfm_ba_options *o) {
   // Ceres' SPARSE_SCHUR is a direct solve by Cholesky, which nobody refines -- plus a line search; its residual lands between 1e-10 and 1e-7
   // (conditioning x the rounding of the explicit block inverses), so the 1e-10 stop bought a second mat-vec + walk in two LM iterations of
   // three for nothing the trajectory can see: cost histories with and without the rule agree to 4e-16 over 20 iterations at configs[4], both
-  // are 1.3e-13 from the oracle's at configs[2] (profiles/r06_pcg_tolerance.json).  With an INEXACT preconditioner a 1e-6 residual is not a
+  // are 1.3e-13 from the oracle's at configs[2] (profiles/r06_pcg_direct_tolerance.json).  With an INEXACT preconditioner a 1e-6 residual is not a
   // direct solve's and does show (1e-6 in the cost on a 108-unknown border): those solves keep iterating to pcg_tolerance.
   o->pcg_direct_tolerance = 1e-6;
   o->pcg_max_iterations = 1000;
@@ -5059,11 +5656,10 @@ extern "C" int osfm_ba_solve(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_op
   return rc;
 }
 
-static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_options *O, osfm_ba_report *Rp, const GenInput *G) {
-  OSFM_REQUIRE(ctx && P && O && Rp, OSFM_E_INVALID, "osfm_ba_solve: null argument");
-  const BaSwitches sw;
-  const bool gen = G != nullptr;
-  if (gen) {
+// ---- the phases of a solve's set-up, in the order ba_solve_impl calls them ------------------------------------------------------------
+// the caller's arguments; touches neither the device nor the report
+static int validate_problem(const osfm_ba_problem *P, const osfm_ba_options *O, const GenInput *G) {
+  if (G) {
     OSFM_REQUIRE(P->n_cameras > 0 && P->n_shots > 0 && P->n_points >= 0 && P->n_obs >= 0, OSFM_E_INVALID, "empty bundle problem");
     OSFM_REQUIRE(P->shot_pose && (P->n_points == 0 || P->points) && (P->n_obs == 0 || (P->obs_shot && P->obs_point && P->obs_xy && P->obs_sigma && G->obs_view)),
                  OSFM_E_INVALID, "osfm_bundle_solve: a required array is null");
@@ -5074,13 +5670,13 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
                  OSFM_E_INVALID, "osfm_ba_solve: a required array is null");
   }
   OSFM_REQUIRE(O->loss >= 0 && O->loss <= 3, OSFM_E_INVALID, "unknown loss %d (bundle_adjuster.cc:427 throws)", O->loss);
-  const auto t_start = std::chrono::steady_clock::now();
-  memset(Rp, 0, sizeof(*Rp));
-  OSFM_CTX_LOCK(ctx);
-  OSFM_HIP(hipSetDevice(ctx->device));
+  return OSFM_OK;
+}
+
+// ... and every index in them
+static int validate_indices(const osfm_ba_problem *P, bool gen) {
   const int S = P->n_shots, NP = P->n_points, NC = P->n_cameras;
   const long M = P->n_obs;
-  const long G_rows0 = gen ? G->rows0 : M;
   for (long o = 0; o < M; o++) {
     OSFM_REQUIRE(P->obs_shot[o] >= 0 && P->obs_shot[o] < S && P->obs_point[o] >= 0 && P->obs_point[o] < NP, OSFM_E_INVALID,
                  "observation %ld references shot %d / point %d", o, P->obs_shot[o], P->obs_point[o]);
@@ -5099,179 +5695,163 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     OSFM_REQUIRE(P->shot_camera[s] >= 0 && P->shot_camera[s] < NC, OSFM_E_INVALID, "shot %d references camera %d", s, P->shot_camera[s]);
 
   OSFM_REQUIRE(M < (1L << 31), OSFM_E_UNSUPPORTED, "more than 2^31 observations");
+  return OSFM_OK;
+}
 
-  // ---- device image ----
-  Arena A;
-  A.ctx = ctx;
-  hipError_t e = hipSuccess;
-  Solver sv;
-  sv.ctx = ctx;
-  sv.st = ctx->stream;
-  A.st = sv.st;
-  // the side stream and its two events live in the context (creating and destroying a stream per solve is a millisecond of a local
-  // bundle adjustment's call); (a low-priority side stream was measured: no difference)
-  // (round 6, measured and dropped: the side stream confined to 192 / 128 / 64 CUs by hipExtStreamCreateWithCUMask so that the cyclic
-  //  reduction's 117 KB workgroups find free LDS elsewhere -- 2.93 - 2.98 ms per LM iteration at configs[4] for every mask, as without one:
-  //  profiles/r06_ba_variants4_side_cu_mask.json)
-  if (!ctx->stream_b) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-  for (int q = 0; q < 2; q++)
-    if (!ctx->ev_side[q]) OSFM_HIP(hipEventCreateWithFlags(&ctx->ev_side[q], hipEventDisableTiming));
-  sv.st2 = ctx->stream_b;
-  sv.ev_fork = ctx->ev_side[0];
-  sv.ev_join = ctx->ev_side[1];
-  sv.loss = O->loss;
-  sv.loss_a = O->loss_threshold;
-  Dev &d = sv.d;
-  memset(&d, 0, sizeof(d));
-  d.S = S; d.P = NP; d.NC = NC; d.M = M;
-  d.cam0 = 6 * S;
-  d.gen = gen ? 1 : 0;
-  GenDev &g = d.g;
+// Generic mode: the border's columns (free rig cameras, free cameras, free biases), per view the slots its rows touch, the decision for the
+// COMPACT rows, and the upload of everything the generic kernels read beyond the instance poses and the points.
+static int gen_border_layout(const osfm_ba_problem *P, const GenInput *G, Arena &A, hipError_t &e, Solver &sv) {
+  GenDev &g = sv.d.g;
+  const BaSwitches &sw = sv.sw;
+  const int S = P->n_shots, NP = P->n_points, NC = P->n_cameras;
+  const long M = P->n_obs;
   std::vector<int> inst_view0;
-  std::vector<unsigned char> gen_col_slot_host;
-  if (gen) {  // border columns: free rig cameras, free cameras, free biases; per view the slots its rows touch
-    const int NV = G->NV, NRC = G->NRC;
-    g.NV = NV;
-    g.NRC = NRC;
-    std::vector<int> cam_col((size_t)NC, -1), rc_col((size_t)NRC, -1), bias_col((size_t)NC, -1);
-    std::vector<unsigned char> rc_useful((size_t)NRC, 1);
-    int nb = 0;
-    bool spherical = false;
-    for (int q = 0; q < NRC; q++) {
-      const bool fixed = G->rc_fixed[q] != 0;
-      bool zero = true;
-      for (int k = 0; k < 6; k++) zero = zero && G->rc_pose[6 * q + k] == 0.0;
-      rc_useful[(size_t)q] = !(fixed && zero);  // IsRigCameraUseful, bundle_adjuster.cc:17-20
-      if (!fixed) {
-        rc_col[(size_t)q] = nb;
-        nb += 6;
-      }
+  const int NV = G->NV, NRC = G->NRC;
+  g.NV = NV;
+  g.NRC = NRC;
+  std::vector<int> cam_col((size_t)NC, -1), rc_col((size_t)NRC, -1), bias_col((size_t)NC, -1);
+  std::vector<unsigned char> rc_useful((size_t)NRC, 1);
+  int nb = 0;
+  bool spherical = false;
+  for (int q = 0; q < NRC; q++) {
+    const bool fixed = G->rc_fixed[q] != 0;
+    bool zero = true;
+    for (int k = 0; k < 6; k++) zero = zero && G->rc_pose[6 * q + k] == 0.0;
+    rc_useful[(size_t)q] = !(fixed && zero);  // IsRigCameraUseful, bundle_adjuster.cc:17-20
+    if (!fixed) {
+      rc_col[(size_t)q] = nb;
+      nb += 6;
     }
-    for (int c = 0; c < NC; c++) {
-      const int nk = model_num_params(G->cam_model[c]);
-      spherical = spherical || G->cam_model[c] == OSFM_CAMERA_SPHERICAL;
-      if (!G->cam_fixed[c] && nk > 0) {
-        cam_col[(size_t)c] = nb;
-        nb += nk;
-      }
-    }
-    for (int c = 0; c < NC; c++)
-      if (G->bias_fixed && !G->bias_fixed[c]) {
-        bias_col[(size_t)c] = nb;
-        nb += 7;
-      }
-    g.NB = nb;
-    g.NRr = spherical ? 3 : 2;
-    sv.gen_uniform_model = G->cam_model[0];
-    for (int c = 1; c < NC; c++)
-      if (G->cam_model[c] != G->cam_model[0]) sv.gen_uniform_model = -1;
-    {  // the COMPACT rows: one 2-D projection type, reprojection rows only, no free rig camera (its six columns are border slots too); OSFM_BA_GEN_FULL_ROWS keeps the slots
-      bool rc_free = false, depth_rows = false;
-      for (int q = 0; q < NRC; q++) rc_free = rc_free || (rc_col[(size_t)q] >= 0 && rc_useful[(size_t)q]);
-      if (G->obs_kind)
-        for (long o = 0; o < M && !depth_rows; o++) depth_rows = G->obs_kind[o] != 0;
-      const int um = sv.gen_uniform_model;
-      sv.gen_compact = !spherical && !rc_free && !depth_rows && !sw.gen_full_rows &&
-                       (um == OSFM_CAMERA_BROWN || um == OSFM_CAMERA_FISHEYE_OPENCV || um == OSFM_CAMERA_PERSPECTIVE);
-    }
-    int KW = 0;
-    auto view_slots = [&](int v, int *cols) {  // returns the number of slots; cols[i] = border column of slot i
-      const int c = G->view_cam[v], q = G->view_rc[v];
-      int n = 0;
-      if (cam_col[(size_t)c] >= 0)
-        for (int k = 0; k < model_num_params(G->cam_model[c]); k++) cols[n++] = cam_col[(size_t)c] + k;
-      if (rc_col[(size_t)q] >= 0 && rc_useful[(size_t)q])
-        for (int k = 0; k < 6; k++) cols[n++] = rc_col[(size_t)q] + k;
-      return n;
-    };
-    int tmp[kGenMaxKW];
-    for (int v = 0; v < NV; v++) KW = std::max(KW, view_slots(v, tmp));
-    g.KW = KW;
-    g.oJp = g.NRr;
-    g.oJc = 4 * g.NRr;
-    g.oJb = 10 * g.NRr;
-    g.ncomp = sv.gen_compact ? g.NRr * 10 + 4 : g.NRr * (10 + KW);  // (COMPACT: Xc | wt in place of the 2 KW border slots)
-    std::vector<int> view_col((size_t)std::max(1, NV * KW), -1);
-    std::vector<unsigned char> col_slot((size_t)std::max(1, nb) * NV, 255);
-    for (int v = 0; v < NV; v++) {
-      const int n = view_slots(v, tmp);
-      for (int i = 0; i < n; i++) {
-        view_col[(size_t)v * KW + i] = tmp[i];
-        col_slot[(size_t)tmp[i] * NV + v] = (unsigned char)i;
-      }
-    }
-    inst_view0.assign((size_t)S + 1, 0);
-    for (int v = 0; v < NV; v++) {
-      OSFM_REQUIRE(G->view_inst[v] >= 0 && G->view_inst[v] < S && (v == 0 || G->view_inst[v] >= G->view_inst[v - 1]), OSFM_E_INVALID,
-                   "generic bundle: the views are not grouped by instance");
-      inst_view0[(size_t)G->view_inst[v] + 1]++;
-    }
-    for (int i = 0; i < S; i++) inst_view0[(size_t)i + 1] += inst_view0[(size_t)i];
-    g.view_inst = A.upload(G->view_inst, (size_t)NV, e);
-    g.view_rc = A.upload(G->view_rc, (size_t)NV, e);
-    g.view_cam = A.upload(G->view_cam, (size_t)NV, e);
-    g.view_col = A.upload(view_col.data(), view_col.size(), e);
-    g.col_slot = A.upload(col_slot.data(), col_slot.size(), e);
-    gen_col_slot_host = col_slot;
-    g.inst_view0 = A.upload(inst_view0.data(), inst_view0.size(), e);
-    g.cam_col = A.upload(cam_col.data(), (size_t)NC, e);
-    g.rc_col = A.upload(rc_col.data(), (size_t)NRC, e);
-    g.bias_col = A.upload(bias_col.data(), (size_t)NC, e);
-    g.rc_useful = A.upload(rc_useful.data(), (size_t)NRC, e);
-    g.cam = A.upload(G->cam, (size_t)16 * NC, e);
-    g.cam_n = A.alloc<double>((size_t)16 * NC, e);
-    g.cam_prior = A.upload(G->cam_prior, (size_t)16 * NC, e);
-    g.cam_sigma = A.upload(G->cam_sigma, (size_t)16 * NC, e);
-    g.bias = A.upload(G->bias, (size_t)7 * NC, e);
-    g.bias_n = A.alloc<double>((size_t)7 * NC, e);
-    g.rc = A.upload(G->rc_pose, (size_t)6 * NRC, e);
-    g.rc_n = A.alloc<double>((size_t)6 * NRC, e);
-    g.rcR = A.alloc<double>((size_t)36 * NRC, e);
-    if (G->rc_prior && G->rc_sigma) {
-      g.rc_prior = A.upload(G->rc_prior, (size_t)6 * NRC, e);
-      g.rc_sigma = A.upload(G->rc_sigma, (size_t)6 * NRC, e);
-    }
-    if (G->gps && G->gps_sigma && G->inst_bias_cam) {
-      g.gps = A.upload(G->gps, (size_t)3 * S, e);
-      g.gps_sigma = A.upload(G->gps_sigma, (size_t)3 * S, e);
-      g.inst_bias_cam = A.upload(G->inst_bias_cam, (size_t)S, e);
-      for (int i = 0; i < S; i++)
-        if (G->gps_sigma[3 * i] > 0 && bias_col[(size_t)G->inst_bias_cam[i]] >= 0) sv.have_bpri = true;
-    }
-    auto per_view = [&](const double *val, const double *sd, int width, const double *&dv, const double *&ds) {
-      if (!val || !sd) return;
-      dv = A.upload(val, (size_t)width * NV, e);
-      ds = A.upload(sd, (size_t)NV, e);
-      for (int v = 0; v < NV; v++)
-        if (sd[v] > 0 && rc_col[(size_t)G->view_rc[v]] >= 0) sv.have_bpri = true;
-    };
-    if (G->up && G->up_sigma)
-      for (int v = 0; v < NV; v++) {
-        const double *u = G->up + 3 * (size_t)v;
-        OSFM_REQUIRE(!(G->up_sigma[v] > 0) || std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) >= 1e-10, OSFM_E_INVALID,
-                     "UpVectorError: acceleration vector has near-zero magnitude");
-      }
-    per_view(G->up, G->up_sigma, 3, g.up, g.up_sigma);
-    per_view(G->pan, G->pan_sigma, 1, g.pan, g.pan_sigma);
-    per_view(G->tilt, G->tilt_sigma, 1, g.tilt, g.tilt_sigma);
-    per_view(G->roll, G->roll_sigma, 1, g.roll, g.roll_sigma);
-    if (G->pt_prior && G->pt_prior_sigma && NP > 0) {
-      g.pt_prior = A.upload(G->pt_prior, (size_t)3 * NP, e);
-      g.pt_prior_sigma = A.upload(G->pt_prior_sigma, (size_t)3 * NP, e);
-      std::vector<unsigned char> alt((size_t)NP, 1);
-      if (G->pt_prior_alt) alt.assign(G->pt_prior_alt, G->pt_prior_alt + NP);
-      g.pt_prior_alt = A.upload(alt.data(), (size_t)NP, e);
-    }
-    g.PI = A.alloc<double>((size_t)36 * S, e);
-    g.Bpri = A.alloc<double>((size_t)std::max(1, nb) * 6 * S, e);
-    g.Cpri = A.alloc<double>((size_t)std::max(1, nb * nb), e);
-    g.gpri = A.alloc<double>((size_t)6 * S + nb, e);
-    g.bdot = A.alloc<double>((size_t)std::max(1, nb) * kBpriSlices, e);
-    g.vpart = A.alloc<double>((size_t)std::max(1, NV * 2 * KW), e);
-    g.yv = A.alloc<double>((size_t)std::max(1, NV * KW), e);
   }
-  const int nbord = gen ? g.NB : 3 * NC;  // border unknowns behind the 6 S of the band
-  d.nred = 6 * S + nbord;
+  for (int c = 0; c < NC; c++) {
+    const int nk = model_num_params(G->cam_model[c]);
+    spherical = spherical || G->cam_model[c] == OSFM_CAMERA_SPHERICAL;
+    if (!G->cam_fixed[c] && nk > 0) {
+      cam_col[(size_t)c] = nb;
+      nb += nk;
+    }
+  }
+  for (int c = 0; c < NC; c++)
+    if (G->bias_fixed && !G->bias_fixed[c]) {
+      bias_col[(size_t)c] = nb;
+      nb += 7;
+    }
+  g.NB = nb;
+  g.NRr = spherical ? 3 : 2;
+  sv.gen_uniform_model = G->cam_model[0];
+  for (int c = 1; c < NC; c++)
+    if (G->cam_model[c] != G->cam_model[0]) sv.gen_uniform_model = -1;
+  {  // the COMPACT rows: one 2-D projection type, reprojection rows only, no free rig camera (its six columns are border slots too); OSFM_BA_GEN_FULL_ROWS keeps the slots
+    bool rc_free = false, depth_rows = false;
+    for (int q = 0; q < NRC; q++) rc_free = rc_free || (rc_col[(size_t)q] >= 0 && rc_useful[(size_t)q]);
+    if (G->obs_kind)
+      for (long o = 0; o < M && !depth_rows; o++) depth_rows = G->obs_kind[o] != 0;
+    const int um = sv.gen_uniform_model;
+    sv.gen_compact = !spherical && !rc_free && !depth_rows && !sw.gen_full_rows &&
+                     (um == OSFM_CAMERA_BROWN || um == OSFM_CAMERA_FISHEYE_OPENCV || um == OSFM_CAMERA_PERSPECTIVE);
+  }
+  int KW = 0;
+  auto view_slots = [&](int v, int *cols) {  // returns the number of slots; cols[i] = border column of slot i
+    const int c = G->view_cam[v], q = G->view_rc[v];
+    int n = 0;
+    if (cam_col[(size_t)c] >= 0)
+      for (int k = 0; k < model_num_params(G->cam_model[c]); k++) cols[n++] = cam_col[(size_t)c] + k;
+    if (rc_col[(size_t)q] >= 0 && rc_useful[(size_t)q])
+      for (int k = 0; k < 6; k++) cols[n++] = rc_col[(size_t)q] + k;
+    return n;
+  };
+  int tmp[kGenMaxKW];
+  for (int v = 0; v < NV; v++) KW = std::max(KW, view_slots(v, tmp));
+  g.KW = KW;
+  g.oJp = g.NRr;
+  g.oJc = 4 * g.NRr;
+  g.oJb = 10 * g.NRr;
+  g.ncomp = sv.gen_compact ? g.NRr * 10 + 4 : g.NRr * (10 + KW);  // (COMPACT: Xc | wt in place of the 2 KW border slots)
+  std::vector<int> view_col((size_t)std::max(1, NV * KW), -1);
+  std::vector<unsigned char> col_slot((size_t)std::max(1, nb) * NV, 255);
+  for (int v = 0; v < NV; v++) {
+    const int n = view_slots(v, tmp);
+    for (int i = 0; i < n; i++) {
+      view_col[(size_t)v * KW + i] = tmp[i];
+      col_slot[(size_t)tmp[i] * NV + v] = (unsigned char)i;
+    }
+  }
+  inst_view0.assign((size_t)S + 1, 0);
+  for (int v = 0; v < NV; v++) {
+    OSFM_REQUIRE(G->view_inst[v] >= 0 && G->view_inst[v] < S && (v == 0 || G->view_inst[v] >= G->view_inst[v - 1]), OSFM_E_INVALID,
+                 "generic bundle: the views are not grouped by instance");
+    inst_view0[(size_t)G->view_inst[v] + 1]++;
+  }
+  for (int i = 0; i < S; i++) inst_view0[(size_t)i + 1] += inst_view0[(size_t)i];
+  g.view_inst = A.upload(G->view_inst, (size_t)NV, e);
+  g.view_rc = A.upload(G->view_rc, (size_t)NV, e);
+  g.view_cam = A.upload(G->view_cam, (size_t)NV, e);
+  g.view_col = A.upload(view_col.data(), view_col.size(), e);
+  g.col_slot = A.upload(col_slot.data(), col_slot.size(), e);
+  sv.gen_col_slot = col_slot;
+  g.inst_view0 = A.upload(inst_view0.data(), inst_view0.size(), e);
+  g.cam_col = A.upload(cam_col.data(), (size_t)NC, e);
+  g.rc_col = A.upload(rc_col.data(), (size_t)NRC, e);
+  g.bias_col = A.upload(bias_col.data(), (size_t)NC, e);
+  g.rc_useful = A.upload(rc_useful.data(), (size_t)NRC, e);
+  g.cam = A.upload(G->cam, (size_t)16 * NC, e);
+  g.cam_n = A.alloc<double>((size_t)16 * NC, e);
+  g.cam_prior = A.upload(G->cam_prior, (size_t)16 * NC, e);
+  g.cam_sigma = A.upload(G->cam_sigma, (size_t)16 * NC, e);
+  g.bias = A.upload(G->bias, (size_t)7 * NC, e);
+  g.bias_n = A.alloc<double>((size_t)7 * NC, e);
+  g.rc = A.upload(G->rc_pose, (size_t)6 * NRC, e);
+  g.rc_n = A.alloc<double>((size_t)6 * NRC, e);
+  g.rcR = A.alloc<double>((size_t)36 * NRC, e);
+  if (G->rc_prior && G->rc_sigma) {
+    g.rc_prior = A.upload(G->rc_prior, (size_t)6 * NRC, e);
+    g.rc_sigma = A.upload(G->rc_sigma, (size_t)6 * NRC, e);
+  }
+  if (G->gps && G->gps_sigma && G->inst_bias_cam) {
+    g.gps = A.upload(G->gps, (size_t)3 * S, e);
+    g.gps_sigma = A.upload(G->gps_sigma, (size_t)3 * S, e);
+    g.inst_bias_cam = A.upload(G->inst_bias_cam, (size_t)S, e);
+    for (int i = 0; i < S; i++)
+      if (G->gps_sigma[3 * i] > 0 && bias_col[(size_t)G->inst_bias_cam[i]] >= 0) sv.have_bpri = true;
+  }
+  auto per_view = [&](const double *val, const double *sd, int width, const double *&dv, const double *&ds) {
+    if (!val || !sd) return;
+    dv = A.upload(val, (size_t)width * NV, e);
+    ds = A.upload(sd, (size_t)NV, e);
+    for (int v = 0; v < NV; v++)
+      if (sd[v] > 0 && rc_col[(size_t)G->view_rc[v]] >= 0) sv.have_bpri = true;
+  };
+  if (G->up && G->up_sigma)
+    for (int v = 0; v < NV; v++) {
+      const double *u = G->up + 3 * (size_t)v;
+      OSFM_REQUIRE(!(G->up_sigma[v] > 0) || std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]) >= 1e-10, OSFM_E_INVALID,
+                   "UpVectorError: acceleration vector has near-zero magnitude");
+    }
+  per_view(G->up, G->up_sigma, 3, g.up, g.up_sigma);
+  per_view(G->pan, G->pan_sigma, 1, g.pan, g.pan_sigma);
+  per_view(G->tilt, G->tilt_sigma, 1, g.tilt, g.tilt_sigma);
+  per_view(G->roll, G->roll_sigma, 1, g.roll, g.roll_sigma);
+  if (G->pt_prior && G->pt_prior_sigma && NP > 0) {
+    g.pt_prior = A.upload(G->pt_prior, (size_t)3 * NP, e);
+    g.pt_prior_sigma = A.upload(G->pt_prior_sigma, (size_t)3 * NP, e);
+    std::vector<unsigned char> alt((size_t)NP, 1);
+    if (G->pt_prior_alt) alt.assign(G->pt_prior_alt, G->pt_prior_alt + NP);
+    g.pt_prior_alt = A.upload(alt.data(), (size_t)NP, e);
+  }
+  g.PI = A.alloc<double>((size_t)36 * S, e);
+  g.Bpri = A.alloc<double>((size_t)std::max(1, nb) * 6 * S, e);
+  g.Cpri = A.alloc<double>((size_t)std::max(1, nb * nb), e);
+  g.gpri = A.alloc<double>((size_t)6 * S + nb, e);
+  g.bdot = A.alloc<double>((size_t)std::max(1, nb) * kBpriSlices, e);
+  g.vpart = A.alloc<double>((size_t)std::max(1, NV * 2 * KW), e);
+  g.yv = A.alloc<double>((size_t)std::max(1, NV * KW), e);
+  return OSFM_OK;
+}
+
+// the parameter blocks and what the priors of the [k1 k2 focal] mode read
+static int upload_blocks(const osfm_ba_problem *P, const GenInput *G, Arena &A, hipError_t &e, Dev &d) {
+  const bool gen = G != nullptr;
+  const int S = P->n_shots, NP = P->n_points, NC = P->n_cameras;
   d.cams = gen ? nullptr : A.upload(P->cam_params, (size_t)3 * NC, e);
   d.poses = A.upload(P->shot_pose, (size_t)6 * S, e);
   d.pts = A.upload(P->points, (size_t)3 * NP, e);
@@ -5302,14 +5882,23 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     d.up_J = A.alloc<double>((size_t)9 * S, e);
     d.prior_rot = A.alloc<double>((size_t)6 * S, e);
   }
+  return OSFM_OK;
+}
+
   // ---- point-major observation order and shot-major index lists, built on the device: perm = stable argsort of the observations by
   //      point (the order a host counting sort gives), shot_obs = stable argsort of the point-major positions by shot; offsets by
   //      lower bounds.  (The host version of this -- five passes with random scatters over 20 MB arrays -- was 35-40 ms of the 60 ms
   //      setup at configs[4].) ----
+// Leaves the orders in d, the permutation in sv.d_perm, the band's true half-width and the matrix-core assembly's point order in the plan,
+// and cuts the points into the workgroups of the cooperative kernels (d.wg_pt).
+static int build_observation_orders(const osfm_ba_problem *P, const GenInput *G, Arena &A, hipError_t &e, Solver &sv, SolvePlan &pl) {
+  Dev &d = sv.d;
+  GenDev &g = d.g;
+  const bool gen = G != nullptr;
+  const int S = P->n_shots, NP = P->n_points;
+  const long M = P->n_obs;
   std::vector<long> pt_off((size_t)NP + 1, 0);
-  int *d_perm = A.alloc<int>((size_t)M, e);
-  int bw_true = 0;
-  int track_repeats_shot = 0;
+  int *const d_perm = sv.d_perm = A.alloc<int>((size_t)M, e);
   int *bp_keys = nullptr, *bp_pts = nullptr;  // the points in the order of the first shot of their track (band_mfma_kernel)
   if (M == 0) {  // (generic mode only) a problem of priors: empty segments everywhere
     long *d_pt_off = A.alloc<long>((size_t)NP + 1, e), *d_shot_off = A.alloc<long>((size_t)S + 1, e), *d_view_off = A.alloc<long>((size_t)g.NV + 1, e);
@@ -5370,8 +5959,8 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       bp_pts = nullptr;
     OSFM_HIP(hipGetLastError());
     OSFM_HIP(hipMemcpyAsync(pt_off.data(), d_pt_off, ((size_t)NP + 1) * sizeof(long), hipMemcpyDeviceToHost, sv.st));
-    OSFM_HIP(hipMemcpyAsync(&bw_true, d_bw, sizeof(int), hipMemcpyDeviceToHost, sv.st));
-    OSFM_HIP(hipMemcpyAsync(&track_repeats_shot, d_bw + 1, sizeof(int), hipMemcpyDeviceToHost, sv.st));
+    OSFM_HIP(hipMemcpyAsync(&pl.bw_true, d_bw, sizeof(int), hipMemcpyDeviceToHost, sv.st));
+    OSFM_HIP(hipMemcpyAsync(&pl.track_repeats_shot, d_bw + 1, sizeof(int), hipMemcpyDeviceToHost, sv.st));
     OSFM_HIP(hipStreamSynchronize(sv.st));
     d.o_shot = o_shot;
     d.o_point = o_point;
@@ -5410,6 +5999,18 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     d.nwg = (int)wg_pt.size() - 1;
     d.wg_pt = A.upload(wg_pt.data(), wg_pt.size(), e);
   }
+  pl.bp_keys = bp_keys;
+  pl.bp_pts = bp_pts;
+  return OSFM_OK;
+}
+
+// the Jacobian copy, the shot-major copies of the observations, and the vectors of the LM / PCG iteration
+static void alloc_work_vectors(Arena &A, hipError_t &e, Solver &sv, int nbord) {
+  Dev &d = sv.d;
+  GenDev &g = d.g;
+  const bool gen = d.gen != 0;
+  const int S = d.S, NP = d.P, NC = d.NC;
+  const long M = d.M;
   d.shotR = A.alloc<double>((size_t)36 * S, e);
   d.Jpm = A.alloc<double>((size_t)(gen ? g.ncomp : kRowComps) * M, e);
   d.sm_wt = A.alloc<double>((size_t)std::max<long>(1, M), e);
@@ -5456,67 +6057,76 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   d.partial2 = A.alloc<double>((size_t)2 * nblk(3L * NP) + 16, e);
   d.dotp = A.alloc<double>((size_t)nblk(d.nred) + NC + 16, e);
   d.rrp = A.alloc<double>((size_t)nblk(d.nred) + 16, e);
+}
+
+// Which solver takes the band, sized and allocated: the exact band in LDS clusters (one workgroup for few shots), the wide band over dense
+// clusters or as a block LDL^T chain, or the truncated band's sequential Cholesky; and how the band is assembled.
+static int choose_band_solver(osfm_ctx *ctx, const osfm_ba_options *O, Arena &A, hipError_t &e, Solver &sv, SolvePlan &pl) {
+  Dev &d = sv.d;
+  GenDev &g = d.g;
+  const BaSwitches &sw = sv.sw;
+  const bool gen = d.gen != 0;
+  const int S = d.S, NP = d.P;
+  const long M = d.M;
   // block half-bandwidth of the shot-shot coupling (shots in caller order): bw_true, from track_width_kernel above
   // half-width up to 10: exact band, cyclic reduction in LDS; up to kWMaxBw: exact band, cyclic reduction over dense clusters (dbcr_*); beyond: truncated to kMaxBw
   // (round 6: the dense-cluster solver takes over where the LDS clusters end, at half-width 11 -- until round 5 at 16, and half-widths 11 .. 15 fell to
   //  the sequential band Cholesky WITHOUT the exact border: 180 - 244 CG iterations per LM iteration on a 27-shot scene with nine free cameras)
   constexpr int kLdsBw = 10;  // widest band whose clusters (6 cs unknowns, cs >= bw) the cyclic reduction holds in LDS
   static_assert(kLdsBw <= kSbMaxBw, "the one-workgroup band factor runs on the LDS clusters' bands");
-  const bool wide = O->preconditioner == 0 && S >= 2 && bw_true > kLdsBw && bw_true <= kWMaxBw;
-  d.bw = O->preconditioner == 1 ? 0 : (wide ? bw_true : std::min(bw_true, kMaxBw));
+  pl.wide = O->preconditioner == 0 && S >= 2 && pl.bw_true > kLdsBw && pl.bw_true <= kWMaxBw;
+  d.bw = O->preconditioner == 1 ? 0 : (pl.wide ? pl.bw_true : std::min(pl.bw_true, kMaxBw));
   if (S < 2) d.bw = 0;
   // band columns per launch of the per-shot assembly: all of them when one copy fits a workgroup's LDS, else equal slices of at most kBandSlice
-  const int band_nslice = (d.bw + 1 + kBandSlice - 1) / kBandSlice, band_slice = (d.bw + 1 + band_nslice - 1) / band_nslice;
-  int band_copies = kBandCopies;  // private copies of the band assembly's LDS accumulators
-  while (band_copies > 1 && (size_t)band_slice * 36 * band_copies * sizeof(double) > 150 * 1024) band_copies /= 2;
+  const int band_nslice = (d.bw + 1 + kBandSlice - 1) / kBandSlice;
+  pl.band_slice = (d.bw + 1 + band_nslice - 1) / band_nslice;
+  pl.band_copies = kBandCopies;  // private copies of the band assembly's LDS accumulators
+  while (pl.band_copies > 1 && (size_t)pl.band_slice * 36 * pl.band_copies * sizeof(double) > 150 * 1024) pl.band_copies /= 2;
   d.band = A.alloc<double>((size_t)S * (d.bw + 1) * 36, e);
   // exact narrow band, one observation per (track, shot): assembled on the matrix cores (band_mfma_kernel), else per shot with LDS atomics
-  const bool win_band = d.bw >= 1 && d.bw <= kMaxBw && d.bw == bw_true && !track_repeats_shot && bp_pts != nullptr && !sw.band_per_shot &&
-                        !(gen && g.NRr == 3);  // (it forms E from the two-row layout of the Jacobian copy)
-  size_t win_lds = 0;
-  int win_grid = 0;
+  pl.win_band = d.bw >= 1 && d.bw <= kMaxBw && d.bw == pl.bw_true && !pl.track_repeats_shot && pl.bp_pts != nullptr && !sw.band_per_shot &&
+                !(gen && g.NRr == 3);  // (it forms E from the two-row layout of the Jacobian copy)
   // the E blocks as an array: the per-shot assembly's operand only (the matrix-core assembly forms them from the Jacobian copy it reads)
-  d.Epm = d.bw > 0 && (!win_band || sw.check_band) ? A.alloc<double>((size_t)18 * M, e) : nullptr;
-  if (win_band) {
+  d.Epm = d.bw > 0 && (!pl.win_band || sw.check_band) ? A.alloc<double>((size_t)18 * M, e) : nullptr;
+  if (pl.win_band) {
     const int TL = d.bw + 1;
     d.bpNT = (6 * TL + 15) / 16;
     d.bpPC = kBmSlots / TL;
     d.bpR = (int)std::min<long>(8, std::max<long>(1, ((long)NP + 128L * S - 1) / (128L * S)));
-    win_grid = S * d.bpR;
-    win_lds = (size_t)2 * 36 * kBmStride * sizeof(double);
+    pl.win_grid = S * d.bpR;
+    pl.win_lds = (size_t)2 * 36 * kBmStride * sizeof(double);
     int *off = A.alloc<int>((size_t)S + 1, e), *o0 = A.alloc<int>((size_t)NP, e), *ln = A.alloc<int>((size_t)NP, e);
     unsigned char *tpos = A.alloc<unsigned char>((size_t)16 * NP, e);
-    d.bp_part = A.alloc<double>((size_t)win_grid * (d.bpNT * (d.bpNT + 1) / 2) * 256, e);
-    d.bp_pts = bp_pts;
+    d.bp_part = A.alloc<double>((size_t)pl.win_grid * (d.bpNT * (d.bpNT + 1) / 2) * 256, e);
+    d.bp_pts = pl.bp_pts;
     d.bp_off = off;
     d.bp_o0 = o0;
     d.bp_last = ln;
     d.bp_pos = tpos;
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(slab_bound_kernel, dim3(nblk(S + 1L)), dim3(TPB), 0, sv.st, bp_keys, NP, 1, S, off);
-      hipLaunchKernelGGL(sorted_tracks_kernel, dim3(nblk(NP)), dim3(TPB), 0, sv.st, bp_pts, bp_keys, d.pt_off, d.o_shot, NP, o0, ln, tpos);
+      hipLaunchKernelGGL(slab_bound_kernel, dim3(nblk(S + 1L)), dim3(TPB), 0, sv.st, pl.bp_keys, NP, 1, S, off);
+      hipLaunchKernelGGL(sorted_tracks_kernel, dim3(nblk(NP)), dim3(TPB), 0, sv.st, pl.bp_pts, pl.bp_keys, d.pt_off, d.o_shot, NP, o0, ln, tpos);
     }
   }
   // per-shot assembly with accumulators over the partners a shot really has (band_assemble_compact_kernel): tables once, at setup
   d.bslot = nullptr;
-  int bslot_n = 0, bslot_copies = 1;
-  if (d.bw > kMaxBw && !win_band) {
+  if (d.bw > kMaxBw && !pl.win_band) {
     unsigned char *tab = A.alloc<unsigned char>((size_t)S * (d.bw + 1), e);
     int *d_mx = A.alloc<int>(1, e);
     OSFM_REQUIRE(e == hipSuccess, OSFM_E_NOMEM, "BA device allocation/upload failed: %s", hipGetErrorString(e));
     OSFM_HIP(hipMemsetAsync(d_mx, 0, sizeof(int), sv.st));
     hipLaunchKernelGGL(band_slots_kernel, dim3(S), dim3(TPB), (size_t)(d.bw + 1) * sizeof(int), sv.st, d, tab, d_mx);
-    OSFM_HIP(hipMemcpyAsync(&bslot_n, d_mx, sizeof(int), hipMemcpyDeviceToHost, sv.st));
+    OSFM_HIP(hipMemcpyAsync(&pl.bslot_n, d_mx, sizeof(int), hipMemcpyDeviceToHost, sv.st));
     OSFM_HIP(hipStreamSynchronize(sv.st));
-    if (bslot_n >= 1 && bslot_n <= 64) {  // (more distinct partners than that: the full rows, in slices)
+    if (pl.bslot_n >= 1 && pl.bslot_n <= 64) {  // (more distinct partners than that: the full rows, in slices)
       d.bslot = tab;
-      bslot_copies = kBandCopies;
-      while (bslot_copies > 1 && (size_t)bslot_n * 36 * bslot_copies * sizeof(double) + d.bw + 1 > 72 * 1024) bslot_copies /= 2;  // two workgroups per CU
+      pl.bslot_copies = kBandCopies;
+      while (pl.bslot_copies > 1 && (size_t)pl.bslot_n * 36 * pl.bslot_copies * sizeof(double) + d.bw + 1 > 72 * 1024) pl.bslot_copies /= 2;  // two workgroups per CU
     }
   }
   d.dinv = A.alloc<double>((size_t)S * 36, e);
   d.cs = 0; d.ncl = 0; d.ncd = 0;
-  if (d.bw >= 1 && d.bw <= kLdsBw && d.bw == bw_true && O->preconditioner == 0) {  // exact band, dense clusters fit LDS
+  if (d.bw >= 1 && d.bw <= kLdsBw && d.bw == pl.bw_true && O->preconditioner == 0) {  // exact band, dense clusters fit LDS
     d.cs = d.bw < 2 ? 2 : d.bw;
     d.ncd = 6 * d.cs;
     d.ncl = (S + d.cs - 1) / d.cs;
@@ -5541,8 +6151,8 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
   d.wNB = 0; d.wWb = 0;
   d.qN = 0; d.qm = 0; d.qcs = 0;
   // wide band: cyclic reduction over dense clusters (dbcr_*); OSFM_BA_WIDE_LDLT keeps round 3's block LDL^T chain (measurement knob)
-  bool dense_cr = wide && !sw.wide_ldlt;
-  if (dense_cr) {
+  pl.dense_cr = pl.wide && !sw.wide_ldlt;
+  if (pl.dense_cr) {
     // the dense-cluster blocks take ~9 (6 bw)^2 doubles per cluster plus the panel buffers, 2-3 x the LDL^T window's tiles: when the
     // device cannot hold them beside everything already allocated, the block LDL^T chain below (slower, a third of the memory) solves
     // the same band instead of the call failing with OSFM_E_NOMEM.  OSFM_BA_DENSE_CR_BUDGET (bytes) stands in for the free memory in tests.
@@ -5553,9 +6163,9 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     if (sw.dense_cr_budget) free_b = (size_t)atoll(sw.dense_cr_budget);
     else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = ~(size_t)0;
     else free_b += ctx->pool_bytes;  // the context's cached blocks are not "free" to the runtime, but an allocation that fails takes them back
-    if (need > free_b - free_b / 8) dense_cr = false;
+    if (need > free_b - free_b / 8) pl.dense_cr = false;
   }
-  if (dense_cr) {
+  if (pl.dense_cr) {
     d.qcs = d.bw;
     d.qm = 6 * d.qcs;
     d.qN = (S + d.qcs - 1) / d.qcs;
@@ -5577,7 +6187,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       d.qC = A.alloc<double>(nb * d.qT * d.qm, e);
     }
   }
-  if (wide && !dense_cr) {
+  if (pl.wide && !pl.dense_cr) {
     d.wNB = (S + kWcs - 1) / kWcs;
     d.wWb = std::min((d.bw + kWcs - 1) / kWcs, d.wNB - 1);
     const size_t nt = (size_t)d.wNB * (d.wWb + 1) * kWB * kWB;
@@ -5587,7 +6197,19 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     d.wDinv = A.alloc<double>((size_t)d.wNB * kWB * kWB, e);
     d.wx = A.alloc<double>((size_t)d.wNB * kWB * 4, e);  // up to 4 right-hand sides side by side
   }
-  if ((d.ncl > 0 || wide) && nbord >= 1 && nbord <= (gen ? kGenMaxNB : 6)) {  // exact camera border: see border_rhs_kernel
+  return OSFM_OK;
+}
+
+// The exact camera border's buffers (when the band is exact and the border small enough), then the plan's loop-invariant predicates: every
+// input of theirs is fixed from here on.
+static int plan_border_and_iteration(const osfm_ba_problem *P, const osfm_ba_options *O, const GenInput *G, Arena &A, hipError_t &e, Solver &sv, SolvePlan &pl) {
+  Dev &d = sv.d;
+  GenDev &g = d.g;
+  const bool gen = G != nullptr;
+  const int S = d.S, NC = d.NC;
+  const long M = d.M;
+  const int nbord = pl.nbord;
+  if ((d.ncl > 0 || pl.wide) && nbord >= 1 && nbord <= (gen ? kGenMaxNB : 6)) {  // exact camera border: see border_rhs_kernel
     sv.Bc = A.alloc<double>((size_t)nbord * 6 * S, e);
     sv.Wb = A.alloc<double>((size_t)nbord * 6 * S, e);
     sv.SigInv = A.alloc<double>((size_t)nbord * nbord, e);
@@ -5601,7 +6223,7 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       std::vector<int> cols, col_pos((size_t)nbord, -1);
       for (int j = 0; j < nbord; j++) {
         bool held = false;
-        for (int v = 0; v < G->NV && !held; v++) held = gen_col_slot_host[(size_t)j * G->NV + v] != 255;
+        for (int v = 0; v < G->NV && !held; v++) held = sv.gen_col_slot[(size_t)j * G->NV + v] != 255;
         if (held) {
           col_pos[(size_t)j] = (int)cols.size();
           cols.push_back(j);
@@ -5615,658 +6237,34 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
       sv.g_vpartB = A.alloc<double>((size_t)std::max(1, G->NV) * std::max(1, sv.g_ncols) * std::max(1, g.KW), e);
     }
   }
-  bool border_ok = true;  // exact camera border: every camera free (generic mode: the border holds free blocks only)
-  bool all_cams_fixed = !gen;
+  pl.all_cams_fixed = !gen;  // (border_ok starts true: in generic mode the border holds free blocks only)
   for (int c = 0; c < NC && !gen; c++) {
-    if (P->cam_fixed[c]) border_ok = false;
-    else all_cams_fixed = false;
+    if (P->cam_fixed[c]) pl.border_ok = false;
+    else pl.all_cams_fixed = false;
   }
-  sv.cams_inert = all_cams_fixed;
-  if (all_cams_fixed && e == hipSuccess) OSFM_HIP(hipMemsetAsync(d.camred, 0, (size_t)9 * NC * sizeof(double), sv.st));
-  int *d_status = A.alloc<int>(4, e);
-  double *d_reproj = (gen ? G->reproj3 != nullptr : P->reproj_err != nullptr) ? A.alloc<double>((size_t)(gen ? 3 : 2) * M, e) : nullptr;
-  OSFM_REQUIRE(e == hipSuccess, OSFM_E_NOMEM, "BA device allocation/upload failed: %s", hipGetErrorString(e));
-  OSFM_HIP(hipMemsetAsync(d.scal, 0, 32 * sizeof(double), sv.st));
+  sv.cams_inert = pl.all_cams_fixed;
+  if (pl.all_cams_fixed && e == hipSuccess) OSFM_HIP(hipMemsetAsync(d.camred, 0, (size_t)9 * NC * sizeof(double), sv.st));
+  pl.try_bcr = d.bw > 0 && d.ncl > 0 && O->preconditioner == 0;
+  pl.try_border = (pl.try_bcr || pl.wide) && sv.Bc && pl.border_ok;
+  pl.want_border = d.bw > 0 && (d.ncl > 0 || pl.wide) && O->preconditioner == 0 && sv.Bc && pl.border_ok;
+  pl.sband_fuse = sv.use_sband && !gen && pl.all_cams_fixed && d.bw > 0 && d.ncl > 0 && O->preconditioner == 0 && !pl.want_border;
+  pl.side2 = pl.sband_fuse ? nullptr : sv.st2;
+  pl.fork_at = pl.sband_fuse ? 0 : pl.win_band ? (d.ncl > 1 && O->preconditioner == 0 ? 2 : 1) : 0;
+  pl.fork_in_bcr = pl.fork_at == 2 && pl.side2 && d.bw > 0 && d.ncl > 1 && O->preconditioner == 0;
+  pl.exact_expected = (pl.try_bcr || pl.wide) && (pl.try_border || (gen ? g.NB == 0 : pl.all_cams_fixed)) && O->pcg_direct_tolerance > O->pcg_tolerance;
+  return OSFM_OK;
+}
 
+// outputs: parameters, reprojection errors (sigma = 1) in the caller's observation order
+static int write_outputs(osfm_ba_problem *P, const GenInput *G, Arena &A, hipError_t &e, Solver &sv) {
+  Dev &d = sv.d;
+  GenDev &g = d.g;
+  const bool gen = G != nullptr;
+  const int S = d.S, NP = d.P, NC = d.NC;
+  const long M = d.M;
   hipStream_t st = sv.st;
-  const int nred = d.nred;
-  const int nbr = nblk(nred);
-  {
-    const int rcp = sv.pinned(nbr, sw);
-    if (rcp != OSFM_OK) return rcp;
-  }
-  double *hs = sv.hscal;
-  OSFM_HIP(hipStreamSynchronize(sv.st));
-  const auto t_run = std::chrono::steady_clock::now();  // from here: what ceres::Solve would cover
-  double cost = 0, sumsq = 0;
-  int rc = sv.eval(d.cams, d.poses, d.pts, true, &cost, &sumsq);
-  if (rc != OSFM_OK) return rc;
-  Rp->initial_cost = cost;
-  Rp->seconds_setup = std::chrono::duration<double>(t_run - t_start).count();
-  Rp->rmse_normalized_initial = std::sqrt(sumsq / (double)std::max<long>(1, gen ? G_rows0 : M));
-  Rp->cost_history[0] = cost;
-  auto mark = [&](const char *what) -> int {
-    if (!sw.trace) return OSFM_OK;
-    fprintf(stderr, "[osfm_ba trace] %s ...", what);
-    fflush(stderr);
-    OSFM_HIP(hipStreamSynchronize(st));
-    OSFM_HIP(hipStreamSynchronize(sv.st2));
-    OSFM_HIP(hipGetLastError());
-    fprintf(stderr, " done\n");
-    return OSFM_OK;
-  };
-  if (mark("first evaluation") != OSFM_OK) return OSFM_E_HIP;
-  double radius = O->initial_radius > 0 ? O->initial_radius : 1e4;
-  double decrease_factor = 2.0;
-  bool need_prepare = true, have_scale = false;
-  bool fast_ok = !sw.no_fast;  // the straight-line iteration is tried (until it fails once in this solve)
-  int n_invalid = 0, iter = 0;
-  double gmax = 0;
-  Rp->termination = 0;
-  double lin_seconds = 0;
-
-  // after a Jacobian evaluation: gradients, (first time) the Jacobi scaling, the LM diagonal and max |gradient| into scal[10]
-  auto prepare_enqueue = [&]() -> int {
-    sv.gradients();
-    if (!have_scale) {
-      hipLaunchKernelGGL(scale_init_kernel, dim3(nblk(std::max<long>(nred, 3L * NP))), dim3(TPB), 0, st, d);
-      have_scale = true;
-    }
-    if (gen) OSFM_HIP(hipMemsetAsync(d.scal + 10, 0, sizeof(double), st));  // (the [k1 k2 focal] mode: cleared by prior_cost_kernel, which every evaluation runs)
-    if (std::max<long>(nred, 3L * NP) <= 65536) {  // small problems: the LM diagonal and max |gradient| in one launch (at configs[4] size the fused kernel was 34 us against 10 + 13)
-      hipLaunchKernelGGL(lm_diag_absmax_kernel, dim3((unsigned)nblk(std::max<long>(nred, 3L * NP))), dim3(256), 0, st, d, d.scal + 10);
-    } else {
-      hipLaunchKernelGGL(lm_diag_kernel, dim3(nblk(std::max<long>(nred, 3L * NP))), dim3(TPB), 0, st, d);
-      hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, st, d.g_red, (long)nred, d.g_pt, 3L * NP, d.scal + 10);
-    }
-    return OSFM_OK;
-  };
-  for (;;) {
-    if (need_prepare) {
-      const int rcp = prepare_enqueue();
-      if (rcp != OSFM_OK) return rcp;
-      {
-        const int rcf = sv.fetch(d.scal + 10, 1, 0);
-        if (rcf != OSFM_OK) return rcf;
-      }
-      gmax = hs[0];
-      need_prepare = false;
-    }
-    if (iter >= O->max_iterations) { Rp->termination = 0; break; }
-    if (gmax <= O->gradient_tolerance) { Rp->termination = 2; break; }
-    if (radius < 1e-32) { Rp->termination = 4; break; }
-    iter++;
-    if (mark("gradients / scaling") != OSFM_OK) return OSFM_E_HIP;
-    if (iter < 256) Rp->cost_history[iter] = cost;  // every exit below (tolerances, invalid step) leaves the slot of this iteration defined
-    const auto t_lin = std::chrono::steady_clock::now();
-    // ---- linear solve: PCG on the implicit Schur complement ----
-    hipLaunchKernelGGL(point_hhat_kernel, dim3(nblk(NP)), dim3(TPB), 0, st, d, radius);
-    sv.use_band = false;
-    sv.cur_radius = radius;
-    // ---- fork: camera-border columns (if this problem uses them) and the right-hand side only need the Jacobian and Hhat: they run on
-    //      the side stream next to the band assembly (a gather that leaves HBM bandwidth unused), so that the cyclic-reduction levels
-    //      -- workgroups that need a whole CU's LDS -- find the CUs free afterwards ----
-    const bool want_border = d.bw > 0 && (d.ncl > 0 || wide) && O->preconditioner == 0 && sv.Bc && border_ok;
-    // few shots, constant cameras: the one-workgroup factorisation carries the solve, so the right-hand side goes in front of it, on the main stream -- the
-    // side stream has nothing to do in such an iteration (side2 = null)
-    const bool sband_fuse = sv.use_sband && !gen && all_cams_fixed && d.bw > 0 && d.ncl > 0 && O->preconditioner == 0 && !want_border;
-    hipStream_t side2 = sband_fuse ? nullptr : sv.st2;
-    hipStream_t sx = side2 ? side2 : st;
-    // where the side stream starts: the per-shot assembly (LDS atomics) leaves HBM idle, so the border's passes run beside it; the
-    // matrix-core assembly fills the CUs (four workgroups of 39 KB LDS each), and the side stream starts after it, beside the cyclic
-    // reduction's levels -- one 117 KB workgroup per CU, which leaves the CU room for a border workgroup
-    // (round 6: with the matrix-core assembly the side stream starts behind the FIRST LEVEL of the cyclic reduction -- its 278 workgroups of 117 KB
-    //  LDS need every CU twice over, the later levels leave half of them and more to the border's kernels: 3.13 -> 3.09 ms per LM iteration at
-    //  configs[4], profiles/r06_ba_variants.json; everything on one stream: 3.31)
-    int fork_at = win_band ? (d.ncl > 1 && O->preconditioner == 0 ? 2 : 1) : 0;  // 0: before the assembly, 1: after it, 2: after the first level of the cyclic reduction
-    sv.sband_solved = false;
-    if (sband_fuse) {  // (three launches of ~17 us in all: on the main stream, in front of the assembly -- a fork and a join cost as much in event latencies)
-      hipLaunchKernelGGL(schur_point_coop_kernel<1>, dim3(d.nwg), dim3(kCoopObs), 0, st, d, d.y);
-      sv.schur_shot(st);
-      hipLaunchKernelGGL(schur_finish_kernel, dim3(sv.matvec_parts()), dim3(TPB), 0, st, d, (const double *)d.x, (const double *)d.y, d.b, radius, 1, sv.cams_inert ? 1 : 0,
-                         (double *)nullptr);
-      fork_at = 0;
-    }
-    const bool fork_late = fork_at >= 1;
-    if (side2 && !fork_late) {
-      OSFM_HIP(hipEventRecord(sv.ev_fork, st));
-      OSFM_HIP(hipStreamWaitEvent(side2, sv.ev_fork, 0));
-    }
-    if (d.bw > 0) {
-      static OsfmPerDeviceOnce once;
-      const int rca = once.run(ctx->device, []() -> int {
-        OSFM_HIP(hipFuncSetAttribute((const void *)band_assemble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        OSFM_HIP(hipFuncSetAttribute((const void *)wide_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return OSFM_OK;
-      });
-      if (rca != OSFM_OK) return rca;
-      if (win_band) {
-        static OsfmPerDeviceOnce once_w;
-        const int rcw = once_w.run(ctx->device, []() -> int {
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_mfma_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-          return OSFM_OK;
-        });
-        if (rcw != OSFM_OK) return rcw;
-        switch (d.bpNT) {
-          case 1: hipLaunchKernelGGL(band_mfma_kernel<1>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-          case 2: hipLaunchKernelGGL(band_mfma_kernel<2>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-          case 3: hipLaunchKernelGGL(band_mfma_kernel<3>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-          case 4: hipLaunchKernelGGL(band_mfma_kernel<4>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-          case 5: hipLaunchKernelGGL(band_mfma_kernel<5>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-          default: hipLaunchKernelGGL(band_mfma_kernel<6>, dim3(win_grid), dim3(384), win_lds, st, d); break;
-        }
-        hipLaunchKernelGGL(band_finish_kernel, dim3(nblk((long)S * (d.bw + 1) * 36)), dim3(TPB), 0, st, d, radius);
-        if (sw.check_band) {  // self-check knob of the tests: the per-shot kernel must agree to rounding
-          const size_t nbd = (size_t)S * (d.bw + 1) * 36;
-          std::vector<double> b_win(nbd), b_shot(nbd);
-          OSFM_HIP(hipMemcpyAsync(b_win.data(), d.band, nbd * sizeof(double), hipMemcpyDeviceToHost, st));
-          hipLaunchKernelGGL(band_assemble_kernel, dim3(S), dim3(TPB), (size_t)(d.bw + 1) * 36 * band_copies * sizeof(double), st, d, radius, band_copies, 0,
-                             d.bw + 1);
-          OSFM_HIP(hipMemcpyAsync(b_shot.data(), d.band, nbd * sizeof(double), hipMemcpyDeviceToHost, st));
-          OSFM_HIP(hipStreamSynchronize(st));
-          double amax = 0, dmax = 0;
-          for (size_t q = 0; q < nbd; q++) {
-            amax = std::max(amax, std::fabs(b_shot[q]));
-            dmax = std::max(dmax, std::fabs(b_shot[q] - b_win[q]));
-          }
-          OSFM_REQUIRE(dmax <= 1e-10 * amax, OSFM_E_NUMERIC, "band_mfma_kernel differs from band_assemble_kernel: max |diff| %.3e against max |entry| %.3e",
-                       dmax, amax);
-          OSFM_HIP(hipMemcpyAsync(d.band, b_win.data(), nbd * sizeof(double), hipMemcpyHostToDevice, st));
-          OSFM_HIP(hipStreamSynchronize(st));
-        }
-      } else if (d.bslot) {
-        static OsfmPerDeviceOnce once_c;
-        const int rcc = once_c.run(ctx->device, []() -> int {
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_assemble_compact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          return OSFM_OK;
-        });
-        if (rcc != OSFM_OK) return rcc;
-        hipLaunchKernelGGL(band_assemble_compact_kernel, dim3(S), dim3(TPB), (size_t)bslot_n * 36 * bslot_copies * sizeof(double) + ((d.bw + 1 + 15) / 16) * 16, st, d,
-                           radius, bslot_copies, bslot_n);
-      } else {
-        for (int lo = 0; lo <= d.bw; lo += band_slice)
-          hipLaunchKernelGGL(band_assemble_kernel, dim3(S), dim3(TPB), (size_t)std::min(band_slice, d.bw + 1 - lo) * 36 * band_copies * sizeof(double), st, d,
-                             radius, band_copies, lo, std::min(band_slice, d.bw + 1 - lo));
-      }
-      sv.use_ctri = false;
-      sv.use_bcr = false;
-    }
-    if (mark("band assembly") != OSFM_OK) return OSFM_E_HIP;
-    const bool fork_in_bcr = fork_at == 2 && side2 && d.bw > 0 && d.ncl > 1 && O->preconditioner == 0;
-    // the side stream's work: the camera border's columns and the right-hand side, from the point of the main stream where it is called
-    auto side_work = [&](bool fork_here) -> int {
-      if (side2 && fork_here) {
-        OSFM_HIP(hipEventRecord(sv.ev_fork, st));
-        OSFM_HIP(hipStreamWaitEvent(side2, sv.ev_fork, 0));
-      }
-      if (want_border && gen) {
-        sv.gen_border_columns(radius, sx);
-      } else if (want_border) {  // all nb columns of B (and of the camera block C) in one pass over the observations
-        if (3 * NC == 3) {
-          hipLaunchKernelGGL(border_point_kernel<3>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, sv.wB);
-          if (sv.shot_waves() > 1) hipLaunchKernelGGL((border_shot_kernel<3, kShotWavesSmall>), dim3(S), dim3(64 * kShotWavesSmall), 0, sx, d, sv.wB, sv.Bc, sv.partB);
-          else hipLaunchKernelGGL((border_shot_kernel<3, 1>), dim3(S), dim3(64), 0, sx, d, sv.wB, sv.Bc, sv.partB);
-          hipLaunchKernelGGL(border_cam_kernel<3>, dim3(NC), dim3(TPB), 0, sx, d, sv.partB, sv.dCm, radius);
-        } else {
-          hipLaunchKernelGGL(border_point_kernel<6>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, sv.wB);
-          if (sv.shot_waves() > 1) hipLaunchKernelGGL((border_shot_kernel<6, kShotWavesSmall>), dim3(S), dim3(64 * kShotWavesSmall), 0, sx, d, sv.wB, sv.Bc, sv.partB);
-          else hipLaunchKernelGGL((border_shot_kernel<6, 1>), dim3(S), dim3(64), 0, sx, d, sv.wB, sv.Bc, sv.partB);
-          hipLaunchKernelGGL(border_cam_kernel<6>, dim3(NC), dim3(TPB), 0, sx, d, sv.partB, sv.dCm, radius);
-        }
-      }
-      // rhs
-      if (sband_fuse) {
-        // (done already, on the main stream)
-      } else if (gen) {
-        sv.gen_rows_apply(1, sx);
-        hipLaunchKernelGGL(gen_schur_finish_kernel, dim3(nbr), dim3(TPB), 0, sx, d, (const double *)d.x, (const double *)d.y, d.b, radius, 1, M > 0 ? 1 : 0, 0, (double *)nullptr);
-      } else {
-        hipLaunchKernelGGL(schur_point_coop_kernel<1>, dim3(d.nwg), dim3(kCoopObs), 0, sx, d, d.y);
-        sv.schur_shot(sx);
-        hipLaunchKernelGGL(schur_finish_kernel, dim3(sv.matvec_parts()), dim3(TPB), 0, sx, d, (const double *)d.x, (const double *)d.y, d.b, radius, 1, sv.cams_inert ? 1 : 0,
-                           (double *)nullptr);
-      }
-      if (side2) OSFM_HIP(hipEventRecord(sv.ev_join, side2));
-      return OSFM_OK;
-    };
-    if (!fork_in_bcr) {
-      const int rcs = side_work(fork_late);
-      if (rcs != OSFM_OK) return rcs;
-    }
-    if (mark("side work (border columns, right-hand side)") != OSFM_OK) return OSFM_E_HIP;
-    bool joined = side2 == nullptr;
-    auto join = [&]() -> int {  // the main stream continues after the side stream's work
-      if (!joined) OSFM_HIP(hipStreamWaitEvent(st, sv.ev_join, 0));
-      joined = true;
-      return OSFM_OK;
-    };
-    // The cyclic reduction (and the camera border on top of it) is issued without asking whether it succeeded: its status words come
-    // back with the first scalars of PCG -- one host round trip for the factorisation, the border and the start of the solve.  When a
-    // status says no (a pivot block that is not positive definite, a singular border) the fallbacks are issued and PCG starts again.
-    const bool try_bcr = d.bw > 0 && d.ncl > 0 && O->preconditioner == 0;
-    const bool try_border = (try_bcr || wide) && sv.Bc && border_ok;
-    sv.use_bcr = false;
-    sv.use_wide = false;
-    sv.use_border = false;
-    bool z_solved = false;  // M^-1 b went through the border's walk
-    auto border_sigma = [&](int nb, int n6) -> int {  // Sigma^-1 = (C - B^T W)^-1 on the device; its status joins the factorisation's
-      hipLaunchKernelGGL(border_dots_kernel, dim3(nb * nb), dim3(TPB), 0, st, sv.Bc, sv.Wb, nb, n6, sv.dots);
-      if (nb <= 6) {
-        hipLaunchKernelGGL(border_sigma_kernel, dim3(1), dim3(64), 0, st, sv.dCm, sv.dots, sv.SigInv, nb, d_status + 1);
-      } else {
-        static OsfmPerDeviceOnce once_s;
-        const int rcs = once_s.run(ctx->device, []() -> int {
-          OSFM_HIP(hipFuncSetAttribute((const void *)gen_border_sigma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));  // (the kernel also has two static words)
-          return OSFM_OK;
-        });
-        if (rcs != OSFM_OK) return rcs;
-        hipLaunchKernelGGL(gen_border_sigma_kernel, dim3(1), dim3(256), (size_t)nb * 2 * nb * sizeof(double), st, (const double *)sv.dCm, (const double *)sv.dots,
-                           sv.SigInv, nb, d_status + 1);
-      }
-      return OSFM_OK;
-    };
-    if (wide) {
-      if (dense_cr) {  // cyclic reduction over dense clusters: log2(S / bw) levels of batched dense operations
-        const int rcq = sv.dbcr_factor(d_status);
-        if (rcq != OSFM_OK) return rcq;
-      } else {  // direct block LDL^T of the exact band: one launch per block column
-        hipLaunchKernelGGL(wide_tiles_kernel, dim3(d.wNB, d.wWb + 1), dim3(256), 0, st, d, d_status);
-        const int ntile = d.wWb * (d.wWb + 1) / 2;
-        for (int J = 0; J < d.wNB; J++) {
-          const int left = std::min(d.wWb, d.wNB - 1 - J);  // rows of the window that exist below block column J
-          hipLaunchKernelGGL(wide_factor_kernel, dim3(1 + (left == d.wWb ? ntile : left * (left + 1) / 2)), dim3(256), (size_t)2 * kWB * kWLd * sizeof(double), st, d, J, d_status);
-        }
-      }
-      sv.use_wide = true;
-      if (try_border) {
-        const int nb = nbord, n6 = 6 * S;
-        const int rcj = join();
-        if (rcj != OSFM_OK) return rcj;
-        sv.wide_solve_set(RhsSet{sv.Bc, n6, sv.Wb, n6, nb + 1, d.b, d.z, nb, gen ? -1 : nb});  // the border's columns and the solve's own right-hand side
-        z_solved = true;
-        const int rcg = border_sigma(nb, n6);
-        if (rcg != OSFM_OK) return rcg;
-        sv.use_border = true;
-      }
-    }
-    if (try_bcr) {
-      const int N = d.ncl;
-      if (sv.use_sband) {  // one workgroup factorises the band; the side stream's work runs beside it
-        static OsfmPerDeviceOnce once;
-        const int rca = once.run(ctx->device, []() -> int {
-          OSFM_HIP(hipFuncSetAttribute((const void *)sband_factor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));  // (+ its two static tables)
-          OSFM_HIP(hipFuncSetAttribute((const void *)sband_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          return OSFM_OK;
-        });
-        if (rca != OSFM_OK) return rca;
-        if (fork_in_bcr) {
-          const int rcs = side_work(true);
-          if (rcs != OSFM_OK) return rcs;
-        }
-        if (sband_fuse) {  // the right-hand side must be there: the side stream was forked before the assembly
-          const int rcj = join();
-          if (rcj != OSFM_OK) return rcj;
-          hipLaunchKernelGGL(sband_factor_kernel, dim3(1), dim3(kSbThreads), sband_factor_lds(S, d.bw), st, d, sv.sbL, d_status, RhsSet{d.b, 0, d.z, 0, 1, nullptr, nullptr, -1, 0},
-                             SbFuse{1, radius, d.x, d.r, d.p, d.y, d.scal + 0, d.scal + 4, d.sc_red});
-          sv.sband_solved = true;
-        } else {
-          hipLaunchKernelGGL(sband_factor_kernel, dim3(1), dim3(kSbThreads), sband_factor_lds(S, d.bw), st, d, sv.sbL, d_status, RhsSet{nullptr, 0, nullptr, 0, 0, nullptr, nullptr, -1, -1},
-                             SbFuse{0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
-        }
-      } else {
-      hipLaunchKernelGGL(bcr_build_kernel, dim3(N), dim3(256), 0, st, d, d_status);
-      const BcrLaunch lv = bcr_level_for(d.cs);
-      {
-        static OsfmPerDeviceOnce once;
-        const int rca = once.run(ctx->device, []() -> int {
-          for (int q = 2; q <= 10; q++)
-            OSFM_HIP(hipFuncSetAttribute((const void *)bcr_level_for(q).fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          return OSFM_OK;
-        });
-        if (rca != OSFM_OK) return rca;
-      }
-      for (int stq = 1; stq < N; stq *= 2) {
-        hipLaunchKernelGGL(lv.fn, dim3((N + 2 * stq - 1) / (2 * stq)), dim3(lv.threads), lv.lds_bytes, st, d, stq, 0, d_status);
-        if (stq == 1 && fork_in_bcr) {
-          const int rcs = side_work(true);
-          if (rcs != OSFM_OK) return rcs;
-        }
-      }
-      hipLaunchKernelGGL(lv.fn, dim3(1), dim3(lv.threads), lv.lds_bytes, st, d, 1, 1, d_status);
-      }
-      sv.use_bcr = true;
-      if (try_border) {  // exact camera border (few cameras, all free): B = S e_j restricted to the shot rows, W = A^-1 B
-        const int nb = nbord, n6 = 6 * S;
-        // the columns of B and C were formed on the side stream; W = A^-1 B for all of them in one walk of the levels
-        const int rcj = join();
-        if (rcj != OSFM_OK) return rcj;
-        for (int q0 = 0; q0 < nb + 1; q0 += kWalkRhs) {  // (the work vectors of a walk hold kWalkRhs right-hand sides)
-          const int cnt = std::min(kWalkRhs, nb + 1 - q0), qx = (nb >= q0 && nb < q0 + cnt) ? nb - q0 : -1;
-          sv.bcr_solve_set(RhsSet{sv.Bc + (long)q0 * n6, n6, sv.Wb + (long)q0 * n6, n6, cnt, d.b, d.z, qx, gen ? -1 : qx});  // the border's columns and the solve's own right-hand side
-        }
-        z_solved = true;
-        const int rcg = border_sigma(nb, n6);
-        if (rcg != OSFM_OK) return rcg;
-        sv.use_border = true;
-      }
-    }
-    auto fallback_band = [&]() -> int {  // sequential banded block Cholesky (truncated band, or the cyclic reduction said no)
-      const int R = d.bw + 1;
-      {
-        static OsfmPerDeviceOnce once;
-        const int rca = once.run(ctx->device, []() -> int {
-          OSFM_HIP(hipFuncSetAttribute((const void *)band_cholesky_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          return OSFM_OK;
-        });
-        if (rca != OSFM_OK) return rca;
-      }
-      hipLaunchKernelGGL(band_cholesky_kernel, dim3(1), dim3(64), (size_t)((kMaxBw + 1) * R * 36 + (kMaxBw + 1) * 36 + 72) * sizeof(double), st, d, d_status);
-      sv.hstat[3] = 1;
-      OSFM_HIP(hipMemcpyAsync(sv.hstat + 3, d_status, sizeof(int), hipMemcpyDeviceToHost, st));
-      OSFM_HIP(hipStreamSynchronize(st));
-      sv.use_band = (sv.hstat[3] == 0);  // a truncated band may lose positive definiteness: fall back to block Jacobi
-      if (sv.use_band && d.ncl > 0) {
-        const size_t n2 = (size_t)d.ncd * d.ncd;
-        OSFM_HIP(hipMemsetAsync(d.cD, 0, (size_t)d.ncl * n2 * sizeof(double), st));
-        OSFM_HIP(hipMemsetAsync(d.cW, 0, (size_t)(d.ncl + 1) * n2 * sizeof(double), st));
-        OSFM_HIP(hipMemsetAsync(d.cWt, 0, (size_t)(d.ncl + 1) * n2 * sizeof(double), st));
-        hipLaunchKernelGGL(ctri_pad_kernel, dim3(1), dim3(64), 0, st, d);
-        hipLaunchKernelGGL(ctri_scatterL_kernel, dim3(S), dim3(TPB), 0, st, d);
-        {
-          static OsfmPerDeviceOnce once;
-          const int rca = once.run(ctx->device, []() -> int {
-            OSFM_HIP(hipFuncSetAttribute((const void *)ctri_inverse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            return OSFM_OK;
-          });
-          if (rca != OSFM_OK) return rca;
-        }
-        hipLaunchKernelGGL(ctri_inverse_kernel, dim3(d.ncl), dim3(64), 2 * n2 * sizeof(double), st, d);
-        sv.use_ctri = true;
-      }
-      return OSFM_OK;
-    };
-    if (d.bw > 0 && !try_bcr && !wide) {
-      const int rcf = fallback_band();
-      if (rcf != OSFM_OK) return rcf;
-    }
-    {
-      const int rcj = join();  // the right-hand side (and its use of part / camred) is complete
-      if (rcj != OSFM_OK) return rcj;
-    }
-    if (mark("factorisation + border solve") != OSFM_OK) return OSFM_E_HIP;
-    int *hst = sv.hstat;
-    hst[0] = hst[1] = hst[2] = 0;
-    auto start_pcg_enqueue = [&]() {
-      // block-Jacobi blocks (6x6 per shot, 3x3 per camera): the fallback preconditioner, and the camera rows of the band
-      // preconditioners -- not needed when the cyclic reduction came out with the exact camera border
-      if (gen) {
-        if (!(sv.use_bcr || sv.use_wide || sv.use_ctri || sv.use_band)) {
-          if (g.NRr == 3) hipLaunchKernelGGL(gen_precond_shot_kernel<3>, dim3(S), dim3(64), 0, st, d, radius);
-          else hipLaunchKernelGGL(gen_precond_shot_kernel<2>, dim3(S), dim3(64), 0, st, d, radius);
-        }
-      } else if (sv.use_bcr && sv.use_sband && !sv.use_border && all_cams_fixed && !z_solved) {
-        // ... and with the one-workgroup band solve the camera blocks, the solve and the start of PCG are ONE launch (three until round 6) --
-        // or none: the factorisation's launch has done it all
-        if (sv.sband_solved) {
-          sv.sband_solved = false;
-          return;
-        }
-        hipLaunchKernelGGL(sband_solve_kernel, dim3(1), dim3(64 * kSbSolveWaves), sband_solve_lds(S, d.bw), st, d, (const double *)sv.sbL,
-                           RhsSet{d.b, 0, d.z, 0, 1, nullptr, nullptr, -1, 0}, SbFuse{1, radius, d.x, d.r, d.p, d.y, d.scal + 0, d.scal + 4, d.sc_red});
-        return;
-      } else if ((sv.use_bcr || sv.use_wide) && all_cams_fixed) {
-        // local / pose-only bundle adjustment: the band is the whole preconditioner and the camera rows are inert (zero scale, zero right-hand
-        // side) -- their 3 x 3 blocks are the LM diagonal alone; the per-shot Schur blocks (63 us per LM iteration on a 48-shot problem) are not needed
-        hipLaunchKernelGGL(precond_cam_kernel, dim3(nblk(NC, 64)), dim3(64), 0, st, d, radius);  // (camred: zeros since setup)
-      } else if (!((sv.use_bcr || sv.use_wide) && sv.use_border)) {
-        hipLaunchKernelGGL(precond_shot_kernel, dim3(S), dim3(64), 0, st, d, radius);
-        hipLaunchKernelGGL(cam_reduce_kernel, dim3(NC), dim3(kCamRedT), 0, st, d, 6, (const double *)nullptr);
-        hipLaunchKernelGGL(precond_cam_kernel, dim3(nblk(NC, 64)), dim3(64), 0, st, d, radius);
-      }
-      sv.precond(d.b, d.z, z_solved);
-      z_solved = false;
-      hipLaunchKernelGGL(pcg_init_kernel, dim3(1), dim3(1024), 0, st, d.b, d.z, d.x, d.r, d.p, nred, d.scal + 0, d.scal + 4, (const double *)d.sc_red, d.y);  // x = 0, r = b, p = z, y = sc p
-    };
-    auto start_pcg = [&]() -> int {
-      start_pcg_enqueue();
-      return sv.fetch(d.scal, 5, 0, d_status, (try_bcr || wide) ? 3 : 0, 0);
-    };
-    // one CG iteration's first half: the mat-vec and x += alpha p, r -= alpha Ap (r . r shares into rrp)
-    auto pcg_half = [&](int rz_cur, bool leave_y = false) {  // leave_y: y = sc x behind the step (the straight-line iteration goes on to the back-substitution)
-      sv.matvec(d.p, d.Ap, radius, true, d.dotp);
-      hipLaunchKernelGGL(pcg_step1_kernel, dim3(nbr), dim3(TPB), 0, st, d.x, d.r, (const double *)d.p, (const double *)d.Ap, nred, (const double *)(d.scal + rz_cur),
-                         (const double *)d.dotp, sv.matvec_parts(), d.scal + 1, d.rrp, (const double *)d.sc_red, leave_y ? d.y : (double *)nullptr);
-    };
-    auto swap_blocks = [&]() {
-      std::swap(d.cams, d.cams_n);
-      std::swap(d.poses, d.poses_n);
-      std::swap(d.pts, d.pts_n);
-      if (gen) {
-        std::swap(g.cam, g.cam_n);
-        std::swap(g.bias, g.bias_n);
-        std::swap(g.rc, g.rc_n);
-      }
-    };
-    auto relinearise_old_point = [&]() -> int {
-      swap_blocks();
-      sv.eval_enqueue(d.cams, d.poses, d.pts, true);
-      return prepare_enqueue();  // (nothing to read: cost, sum of squares and max |gradient| of this point are on the host already)
-    };
-    // Back-substitution, model change, candidate -- and the candidate is LINEARISED before the host has seen the model change (round 6;
-    // rounds 2-5 evaluated its cost alone here and, once the host had accepted the step, came back for the Jacobian): the blocks change
-    // places, the evaluation with Jacobian rows, the gradients, the LM diagonal and max |gradient| are queued behind the back-substitution,
-    // and ONE round trip brings the model change, the step's norms, the candidate's cost and its gradient norm.  An accepted step -- nearly
-    // every step of a converging problem -- has then cost one evaluation instead of two (0.09 ms at configs[4]) and one round trip instead
-    // of two; a rejected or invalid step puts the blocks back and linearises the old point again (the same kernels on the same inputs: the
-    // same bits as before).
-    auto candidate_enqueue = [&](bool y_ready = false) -> int {
-      if (!y_ready) hipLaunchKernelGGL(scale_vec_kernel, dim3(nbr), dim3(TPB), 0, st, d.sc_red, d.x, d.y, nred);
-      if (gen) {
-        if (M > 0 && g.KW > 0) hipLaunchKernelGGL(gen_view_gather_kernel, dim3(nblk((long)g.NV * g.KW)), dim3(TPB), 0, st, d, (const double *)d.y);
-        if (g.NRr == 3) hipLaunchKernelGGL((gen_schur_point_kernel<3, 2>), dim3(d.nwg), dim3(kCoopObs), 0, st, d, (const double *)d.y);
-        else sv.gen_schur_point2(2, st);
-      } else
-        hipLaunchKernelGGL(schur_point_coop_kernel<2>, dim3(d.nwg), dim3(kCoopObs), 0, st, d, d.y);
-      if (gen) hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(1024), 0, st, d.partial, (long)d.nwg, 1, d.scal + 16);  // the model change's observation part
-      if (gen) {
-        hipLaunchKernelGGL(gen_candidate_kernel, dim3(1), dim3(1024), 0, st, d, (const double *)d.y, d.scal + 16);
-        hipLaunchKernelGGL(gen_prior_kernel, dim3(nblk(sv.gen_nprior(), kGenPriorTPB)), dim3(kGenPriorTPB), sv.gen_prior_lds(2), st, d, (const double *)g.cam, (const double *)g.bias,
-                           (const double *)g.rc, (const double *)d.poses, 2, (const double *)d.y, d.scal + 16);
-        if (g.pt_prior_sigma && NP > 0) hipLaunchKernelGGL(gen_point_prior_kernel, dim3(nblk(NP)), dim3(TPB), 0, st, d, (const double *)d.pts, 2, d.scal + 16);
-      }
-      if (gen) {
-        hipLaunchKernelGGL(candidate_points_kernel, dim3(nblk(3L * NP)), dim3(TPB), 0, st, d, d.partial);
-        hipLaunchKernelGGL(finish_reduce_kernel, dim3(1), dim3(1024), 0, st, d.partial, (long)nblk(3L * NP), 2, d.scal + 20);
-      } else {  // the points' candidate first (its shares in partial2), then the cameras' and shots' with both sums and the candidate's rotation blocks
-        hipLaunchKernelGGL(candidate_points_kernel, dim3(nblk(3L * NP)), dim3(TPB), 0, st, d, d.partial2);
-        hipLaunchKernelGGL(candidate_kernel, dim3(1), dim3(1024), 0, st, d, (const double *)d.y, (const double *)d.partial, (long)d.nwg, d.scal + 16,
-                           (const double *)d.partial2, (long)nblk(3L * NP), d.scal + 20, S <= 1024 ? 1 : 0);
-      }
-      swap_blocks();
-      sv.eval_enqueue(d.cams, d.poses, d.pts, true, !gen && S <= 1024);
-      return prepare_enqueue();
-    };
-    bool bad = false;
-    int k = 0;
-    double *rr_part = sv.hrr;
-    const double *dec = hs;  // scal[8 .. 21] of the iteration's last round trip
-    // ---- the straight-line iteration (round 6) ----
-    // With the exact band and the exact border (or constant cameras) the preconditioner is the reduced matrix: CG is one mat-vec, and nothing
-    // the host learns on the way -- the factorisation's status words, |b|, the residual after the first iterate -- changes what is launched
-    // next, except in the rare failure.  So everything is queued back to back: the start of PCG, its first iteration, the back-substitution,
-    // the candidate and its linearisation; ONE round trip brings the status words, the PCG scalars, the shares of r . r, the model change
-    // and the candidate's cost.  When a status word or the residual says no, the blocks go back, the old point is linearised again and the
-    // iteration is redone on the careful path below (which also keeps the fallbacks); after one such failure a solve stays on the careful
-    // path.  Three round trips per LM iteration become one (OSFM_BA_NO_FAST keeps the careful path: the cross-check of the tests).
-    bool fast_done = false;
-    const bool exact_expected = (try_bcr || wide) && (try_border || (gen ? g.NB == 0 : all_cams_fixed)) && O->pcg_direct_tolerance > O->pcg_tolerance;
-    if (exact_expected && fast_ok && !sw.trace) {
-      start_pcg_enqueue();
-      pcg_half(0, true);
-      rc = candidate_enqueue(true);
-      if (rc != OSFM_OK) return rc;
-      {
-        const int rcf = sv.fetch(d.scal, 22, 0, d_status, 3, 0, d.rrp, nbr);
-        if (rcf != OSFM_OK) return rcf;
-      }
-      const double bb1 = hs[4];
-      double rr = 0.0;
-      for (int q = 0; q < nbr; q++) rr += rr_part[(size_t)q];
-      const bool status_ok = !((try_bcr && hst[0] != 0) || (sv.use_wide && hst[2] != 0) || (sv.use_border && hst[1] != 0));
-      const double tol_first = std::max(O->pcg_tolerance, O->pcg_direct_tolerance);
-      const bool forced_failure = sw.fast_fail_at == iter;  // test knob OSFM_BA_FAST_FAIL_AT: the way back to the careful path, exercised on purpose
-      if (!forced_failure && status_ok && bb1 == bb1 && !std::isinf(bb1) && bb1 > 0 && rr == rr && rr <= tol_first * tol_first * bb1) {
-        k = 1;
-        Rp->pcg_iterations_total += 1;
-        dec = hs + 8;
-        fast_done = true;
-      } else {  // back to the old point; the factorisation, the border and the right-hand side stand (the status words are read again below)
-        fast_ok = false;
-        rc = relinearise_old_point();
-        if (rc != OSFM_OK) return rc;
-      }
-    }
-    if (!fast_done) {
-    {
-      const int rcs = start_pcg();
-      if (rcs != OSFM_OK) return rcs;
-    }
-    if ((try_bcr && hst[0] != 0) || (sv.use_wide && hst[2] != 0) || (sv.use_border && hst[1] != 0)) {
-      if (try_bcr && hst[0] != 0) {
-        sv.use_bcr = false;
-        sv.use_border = false;
-        const int rcf = fallback_band();
-        if (rcf != OSFM_OK) return rcf;
-      } else if (sv.use_wide && hst[2] != 0) {  // a pivot block of the wide band is not positive definite: block Jacobi
-        sv.use_wide = false;
-        sv.use_border = false;
-      } else {
-        sv.use_border = false;
-      }
-      const int rcs = start_pcg();
-      if (rcs != OSFM_OK) return rcs;
-    }
-    const double bb = hs[4];
-    bad = !(bb == bb) || std::isinf(bb);
-    if (!bad && bb > 0) {
-      const double tol2 = O->pcg_tolerance * O->pcg_tolerance * bb;
-      // the preconditioner is the reduced matrix itself: the first iterate is a direct solve (see osfm_ba_options_default)
-      const bool exact_precond = (sv.use_bcr || sv.use_wide) && (sv.use_border || (gen ? g.NB == 0 : all_cams_fixed));
-      const double tol2_first = exact_precond ? std::max(tol2, O->pcg_direct_tolerance * O->pcg_direct_tolerance * bb) : tol2;
-      const int kmax = O->pcg_max_iterations > 0 ? O->pcg_max_iterations : 1000;
-      // r.z lives in scal[0] and scal[2] alternately (rz_cur: the current one); p . Ap is added up from the mat-vec's shares by the step kernel
-      int rz_cur = 0, rz_nxt = 2;
-      for (k = 1; k <= kmax; k++) {
-        pcg_half(rz_cur);
-        // the convergence test comes before the preconditioner is applied to the new residual: the last iteration of a solve does not
-        // pay for a walk of the cyclic reduction whose result nobody reads
-        // (an exact band -- with the camera border on top, or with constant cameras as in local bundle adjustment -- makes the
-        // preconditioner the matrix itself: CG is done after one or two iterations, so the first two are polled)
-        if ((k & 3) == 0 || k == kmax || ((sv.use_bcr || sv.use_wide) && k <= 2)) {
-          {
-            const int rcf = sv.fetch(nullptr, 0, 0, nullptr, 0, 0, d.rrp, nbr);
-            if (rcf != OSFM_OK) return rcf;
-          }
-          double rr = 0.0;
-          for (int q = 0; q < nbr; q++) rr += rr_part[(size_t)q];
-          if (!(rr == rr)) { bad = true; break; }
-          if (rr <= (k == 1 ? tol2_first : tol2)) break;
-        }
-        sv.precond(d.r, d.z);
-        hipLaunchKernelGGL(dot2_kernel, dim3(1), dim3(1024), 0, st, d.r, d.z, (const double *)nullptr, (const double *)nullptr, nred,
-                           d.scal + rz_nxt, d.scal + 3);
-        hipLaunchKernelGGL(pcg_step2_kernel, dim3(nbr), dim3(TPB), 0, st, d.p, (const double *)d.z, nred, (const double *)(d.scal + rz_cur), (const double *)(d.scal + rz_nxt),
-                           (const double *)d.sc_red, d.y);
-        std::swap(rz_cur, rz_nxt);
-      }
-      Rp->pcg_iterations_total += k;
-    }
-    if (mark("pcg") != OSFM_OK) return OSFM_E_HIP;
-    if (sw.trace) fprintf(stderr, "[osfm_ba trace] iteration %d: %d pcg iterations, status %d %d %d, band %d bcr %d (one workgroup: %d) wide %d dense %d border %d\n", iter, k, hst[0], hst[1],
-                       hst[2], (int)sv.use_band, (int)sv.use_bcr, (int)(sv.use_bcr && sv.use_sband), (int)sv.use_wide, (int)(sv.use_wide && dense_cr), (int)sv.use_border);
-    rc = candidate_enqueue();
-    if (rc != OSFM_OK) return rc;
-    {
-      const int rcf = sv.fetch(d.scal + 8, 14, 0);  // scal[8..21]
-      if (rcf != OSFM_OK) return rcf;
-    }
-    dec = hs;
-    }  // (careful path)
-    lin_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_lin).count();
-    const double model_change = dec[8];
-    const double step_sq = dec[9] + dec[12], x_sq = dec[10] + dec[13];
-    if (bad || !(model_change > 0)) {  // HandleInvalidStep + StepIsInvalid
-      radius *= 0.5;
-      rc = relinearise_old_point();
-      if (rc != OSFM_OK) return rc;
-      if (++n_invalid >= 5) { Rp->termination = -1; break; }
-      continue;
-    }
-    n_invalid = 0;
-    const double cost_n = dec[0];
-    const double step_norm = std::sqrt(step_sq), x_norm = std::sqrt(x_sq);
-    if (step_norm <= O->parameter_tolerance * (x_norm + O->parameter_tolerance)) {
-      Rp->termination = 3;
-      swap_blocks();  // the step is not taken (the rows and gradients on the device are the candidate's: nothing reads them after the loop)
-      break;
-    }
-    const double cost_change = cost - cost_n;
-    if (std::fabs(cost_change) <= O->function_tolerance * cost) {
-      Rp->termination = 1;
-      swap_blocks();
-      break;
-    }
-    const double rho = cost_change / model_change;
-    if (O->verbose & 1)
-      fprintf(stderr, "[osfm_ba] it %d cost %.9e -> %.9e rho %.3f radius %.3e pcg %d\n", iter, cost, cost_n, rho, radius, k);
-    if (rho > 1e-3) {  // StepAccepted: the blocks are in place and the new point is linearised
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / std::fmax(1.0 / 3.0, 1.0 - t * t * t);
-      radius = std::fmin(1e16, radius);
-      decrease_factor = 2.0;
-      Rp->successful_steps++;
-      cost = dec[0];
-      sumsq = dec[1];
-      gmax = dec[2];
-    } else {  // StepRejected
-      radius = radius / decrease_factor;
-      decrease_factor *= 2.0;
-      rc = relinearise_old_point();
-      if (rc != OSFM_OK) return rc;
-    }
-    if (iter < 256) Rp->cost_history[iter] = cost;
-  }
-  Rp->iterations = iter;
-  Rp->final_cost = cost;
-  Rp->seconds_linear_solver = lin_seconds;
-  OSFM_HIP(hipStreamSynchronize(st));
-  const auto t_tear = std::chrono::steady_clock::now();
-  Rp->seconds_run = std::chrono::duration<double>(t_tear - t_run).count();
-  Rp->preconditioner_bandwidth = (sv.use_band || sv.use_ctri || sv.use_bcr || sv.use_wide) ? d.bw : 0;
-  Rp->shot_bandwidth = bw_true;
-  Rp->ms_matvec_total = 0.0;
-  Rp->matvec_calls = 0;
-  // mat-vec timing sample (HIP events on the solver stream), for the roofline of the dominant kernel: ten extra mat-vecs, only when the
-  // caller asks (OSFM_BA_TIME_MATVEC in options->verbose: the bench does) -- they were 3.9 ms of every configs[4] call's tear-down and as
-  // much as a whole LM iteration of a local bundle adjustment
-  if (O->verbose & OSFM_BA_TIME_MATVEC) {
-    const int reps = 10;
-    hipLaunchKernelGGL(point_hhat_kernel, dim3(nblk(NP)), dim3(TPB), 0, st, d, radius);
-    OSFM_HIP(hipEventRecord(ctx->ev[6], st));
-    for (int i = 0; i < reps; i++) sv.matvec(d.p, d.Ap, radius);
-    OSFM_HIP(hipEventRecord(ctx->ev[7], st));
-    OSFM_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]));
-    Rp->ms_matvec_total = ms;
-    Rp->matvec_calls = reps;
-  }
-  // outputs: parameters, reprojection errors (sigma = 1), NaN/Inf check (ba_helpers.cc:780-814)
+  int *d_perm = sv.d_perm;
+  double *d_reproj = sv.d_reproj;
   sv.rot(d.poses);
   if (gen) {
     hipLaunchKernelGGL(gen_rc_rot_kernel, dim3(nblk(g.NRC, 64)), dim3(64), 0, st, d, (const double *)g.rc);
@@ -6292,9 +6290,91 @@ static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_option
     OSFM_HIP(hipMemcpyAsync(P->reproj_err, d_out, (size_t)2 * M * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   OSFM_HIP(hipStreamSynchronize(st));
-  Rp->rmse_normalized_final = std::sqrt(sumsq / (double)std::max<long>(1, gen ? G_rows0 : M));
+  return OSFM_OK;
+}
+
+static int ba_solve_impl(osfm_ctx *ctx, osfm_ba_problem *P, const osfm_ba_options *O, osfm_ba_report *Rp, const GenInput *G) {
+  OSFM_REQUIRE(ctx && P && O && Rp, OSFM_E_INVALID, "osfm_ba_solve: null argument");
+  OSFM_TRY(validate_problem(P, O, G));
+  const bool gen = G != nullptr;
+  const auto t_start = std::chrono::steady_clock::now();
+  memset(Rp, 0, sizeof(*Rp));
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  OSFM_TRY(validate_indices(P, gen));
+  OSFM_TRY(ba_kernel_attributes(ctx->device));
+  const int S = P->n_shots, NP = P->n_points, NC = P->n_cameras;
+  const long M = P->n_obs;
+  const long rmse_rows = std::max<long>(1, gen ? G->rows0 : M);  // (the depth-prior rows do not count in the RMSE)
+
+  // ---- device image ----
+  Arena A;
+  A.ctx = ctx;
+  hipError_t e = hipSuccess;
+  Solver sv;
+  SolvePlan plan;
+  sv.ctx = ctx;
+  sv.st = ctx->stream;
+  A.st = sv.st;
+  // the side stream and its two events live in the context (creating and destroying a stream per solve is a millisecond of a local
+  // bundle adjustment's call); (a low-priority side stream was measured: no difference)
+  // (round 6, measured and dropped: the side stream confined to 192 / 128 / 64 CUs by hipExtStreamCreateWithCUMask so that the cyclic
+  //  reduction's 117 KB workgroups find free LDS elsewhere -- 2.93 - 2.98 ms per LM iteration at configs[4] for every mask, as without one:
+  //  profiles/r06_ba_variants4_side_cu_mask.json)
+  if (!ctx->stream_b) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
+  for (int q = 0; q < 2; q++)
+    if (!ctx->ev_side[q]) OSFM_HIP(hipEventCreateWithFlags(&ctx->ev_side[q], hipEventDisableTiming));
+  sv.st2 = ctx->stream_b;
+  sv.ev_fork = ctx->ev_side[0];
+  sv.ev_join = ctx->ev_side[1];
+  sv.loss = O->loss;
+  sv.loss_a = O->loss_threshold;
+  Dev &d = sv.d;
+  memset(&d, 0, sizeof(d));
+  d.S = S; d.P = NP; d.NC = NC; d.M = M;
+  d.cam0 = 6 * S;
+  d.gen = gen ? 1 : 0;
+  if (gen) OSFM_TRY(gen_border_layout(P, G, A, e, sv));
+  plan.nbord = gen ? d.g.NB : 3 * NC;
+  d.nred = 6 * S + plan.nbord;
+  OSFM_TRY(upload_blocks(P, G, A, e, d));
+  OSFM_TRY(build_observation_orders(P, G, A, e, sv, plan));
+  alloc_work_vectors(A, e, sv, plan.nbord);
+  OSFM_TRY(choose_band_solver(ctx, O, A, e, sv, plan));
+  OSFM_TRY(plan_border_and_iteration(P, O, G, A, e, sv, plan));
+  sv.d_status = A.alloc<int>(4, e);
+  sv.d_reproj = (gen ? G->reproj3 != nullptr : P->reproj_err != nullptr) ? A.alloc<double>((size_t)(gen ? 3 : 2) * M, e) : nullptr;
+  OSFM_REQUIRE(e == hipSuccess, OSFM_E_NOMEM, "BA device allocation/upload failed: %s", hipGetErrorString(e));
+  OSFM_HIP(hipMemsetAsync(d.scal, 0, 32 * sizeof(double), sv.st));
+  OSFM_TRY(sv.pinned(nblk(d.nred)));
+  OSFM_HIP(hipStreamSynchronize(sv.st));
+
+  // ---- the solve ----
+  const auto t_run = std::chrono::steady_clock::now();  // from here: what ceres::Solve would cover
+  double cost = 0, sumsq = 0, radius = 0;
+  OSFM_TRY(sv.eval(d.cams, d.poses, d.pts, true, &cost, &sumsq));
+  Rp->initial_cost = cost;
+  Rp->seconds_setup = std::chrono::duration<double>(t_run - t_start).count();
+  Rp->rmse_normalized_initial = std::sqrt(sumsq / (double)rmse_rows);
+  Rp->cost_history[0] = cost;
+  OSFM_TRY(sv.mark("first evaluation"));
+  const SolvePlan &pl = plan;  // (constant from here on)
+  OSFM_TRY(sv.lm_loop(pl, O, Rp, &cost, &sumsq, &radius));
+  OSFM_HIP(hipStreamSynchronize(sv.st));
+
+  // ---- report and outputs ----
+  const auto t_tear = std::chrono::steady_clock::now();
+  Rp->seconds_run = std::chrono::duration<double>(t_tear - t_run).count();
+  Rp->preconditioner_bandwidth = (sv.use_band || sv.use_ctri || sv.use_bcr || sv.use_wide) ? d.bw : 0;
+  Rp->shot_bandwidth = pl.bw_true;
+  Rp->ms_matvec_total = 0.0;
+  Rp->matvec_calls = 0;
+  if (O->verbose & OSFM_BA_TIME_MATVEC) OSFM_TRY(sv.time_matvec(radius, Rp));
+  OSFM_TRY(write_outputs(P, G, A, e, sv));
+  Rp->rmse_normalized_final = std::sqrt(sumsq / (double)rmse_rows);
   Rp->seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   Rp->seconds_teardown = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tear).count();
+  // NaN/Inf check (ba_helpers.cc:780-814)
   for (int i = 0; i < (gen ? 16 : 3) * NC; i++)
     OSFM_REQUIRE(std::isfinite(gen ? G->cam[i] : P->cam_params[i]), OSFM_E_NUMERIC, "camera has either NaN or INF values");
   for (long i = 0; i < 6L * S; i++) OSFM_REQUIRE(std::isfinite(P->shot_pose[i]), OSFM_E_NUMERIC, "shot pose has either NaN or INF values");

@@ -1408,10 +1408,7 @@ static int hahog_extract_on_stream(osfm_ctx *ctx, hipStream_t st, const float *i
   const float *d_taps = nullptr;
   double *d_tab = nullptr;  // the constant tables of the context (hahog_tables)
   DescTable *d_dtab = nullptr;
-  {
-    const int rct = hahog_tables(ctx, st, &d_tab, &d_dtab, &d_taps);
-    if (rct != OSFM_OK) return rct;
-  }
+  OSFM_TRY(hahog_tables(ctx, st, &d_tab, &d_dtab, &d_taps));
   const bool two_pass = getenv("OSFM_HAHOG_TWO_PASS") != nullptr;  // measurement / test knob: the separate column and row kernels
   // one level from the previous one; returns 1 when the level's Hessian response (css, factor) came out of the same launch
   auto fused_ok = [&](int slot, int w, int h) { return !(tapW[slot] > kSmMaxW || tapW[slot] < 1 || two_pass || w < 3 || h < 3); };

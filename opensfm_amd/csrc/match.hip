@@ -1126,10 +1126,7 @@ int osfm_launch_match(osfm_ctx *ctx, const osfm_store *store, const int32_t *d_p
   a.pad_tile = store->tile_off[store->n_images];
   OSFM_REQUIRE(a.ncap <= OSFM_MAX_FEATURES, OSFM_E_UNSUPPORTED, "more than %d features in an image", OSFM_MAX_FEATURES);
   OSFM_REQUIRE(n_pairs < (1ll << 31), OSFM_E_INVALID, "too many pairs in one launch");
-  {
-    const int rc = ensure_kernel_attributes(ctx->device);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(ensure_kernel_attributes(ctx->device));
   if (store->is_binary) {
     // bit strings: Hamming distance on the VALU, every pair in one launch; nothing is ever flagged for a second run.
     // matcher_type FLANN on bit strings (round 6; cv2's LSH index searched EXACTLY, as the kd-forest is for floats): knnSearch returns int32

@@ -54,6 +54,13 @@ void osfm_stop_tables(osfm_ctx *ctx, const int64_t *offsets, int n_pairs, double
     }                                                                                       \
   } while (0)
 
+// a call that returns an OSFM_* code: anything but OSFM_OK is passed on to the caller
+#define OSFM_TRY(expr)                  \
+  do {                                  \
+    const int rc_ = (expr);             \
+    if (rc_ != OSFM_OK) return rc_;     \
+  } while (0)
+
 #define OSFM_REQUIRE(cond, code, ...) \
   do {                                \
     if (!(cond)) {                    \

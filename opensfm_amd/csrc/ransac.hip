@@ -589,10 +589,7 @@ int osfm_launch_ransac_pairs(osfm_ctx *ctx, const osfm_store *store, const int32
   const int capr = (cap + 3) & ~3;
   const int lds_pts = std::min(capr, kPairsLdsPts);
   const size_t lds = kRansacFixedLds + (size_t)lds_pts * 16 + 64;
-  {
-    const int rc = ensure_ransac_attributes(ctx->device);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(ensure_ransac_attributes(ctx->device));
   OSFM_HIP(hipMemsetAsync(a.ctl, 0, 64, stream));
   hipLaunchKernelGGL(fransac_draw_kernel, dim3((unsigned)n_pairs), dim3(64), 0, stream, a);
   hipLaunchKernelGGL(fransac_solve_kernel, dim3((unsigned)((n_pairs * kFirst + 63) / 64)), dim3(64), 0, stream, a);
@@ -607,10 +604,7 @@ int osfm_launch_ransac_pairs(osfm_ctx *ctx, const osfm_store *store, const int32
 int osfm_launch_ransac_single(osfm_ctx *ctx, const double *d_p1, const double *d_p2, int n, double thr, double conf,
                               int max_iters, double *d_F, uint8_t *d_mask, int32_t *d_info) {
   const bool in_lds = ((n + 3) & ~3) <= osfm_ransac_lds_points();
-  {
-    const int rc = ensure_ransac_attributes(ctx->device);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(ensure_ransac_attributes(ctx->device));
   if (n < 15)  // cv2 switches to LMedS below 15 correspondences
     hipLaunchKernelGGL(lmeds_single_kernel, dim3(1), dim3(64), 0, ctx->stream, d_p1, d_p2, n, conf, max_iters, d_F, d_mask, d_info);
   else

@@ -251,15 +251,9 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
   if (rounds_out) *rounds_out = 0;
   if (n_pairs == 0) return OSFM_OK;
   const int64_t total = offsets[n_pairs];
-  {
-    const int rc = ensure_relpose_attributes(ctx->device);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(ensure_relpose_attributes(ctx->device));
   RngTable rng;
-  {
-    const int rc = rng_table(ctx, &rng);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(rng_table(ctx, &rng));
   // ShouldStop's bound for every possible best inlier count, with the host libm (see relpose_core.h): one table per distinct pair
   // size n, shared by all pairs of that size (n + 1 pow / log evaluations each), cached on the context
   std::vector<double> stop;

@@ -67,10 +67,7 @@ int run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *
                const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, bool timed_from_ev0, double *kernel_ms) {
   const int64_t total = offsets[n_pairs];
   RngTable rng;
-  {
-    const int rc = osfm_rng_table(ctx, &rng);
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(osfm_rng_table(ctx, &rng));
   std::vector<double> stop;
   std::vector<int64_t> stop_off;
   osfm_stop_tables(ctx, offsets, n_pairs, prm->probability, kMinimalSamples, &stop, &stop_off);
@@ -122,10 +119,7 @@ extern "C" int osfm_relrot_pairs(osfm_ctx *ctx, const double *b1, const double *
                                  const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, double *kernel_ms) {
   if (kernel_ms) *kernel_ms = 0.0;
   OSFM_REQUIRE(ctx, OSFM_E_INVALID, "osfm_relrot_pairs: null context");
-  {
-    const int rc = check_args(offsets, n_pairs, prm, "osfm_relrot_pairs");
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(check_args(offsets, n_pairs, prm, "osfm_relrot_pairs"));
   if (n_pairs == 0) return OSFM_OK;
   OSFM_REQUIRE(b1 && b2 && results, OSFM_E_INVALID, "osfm_relrot_pairs: null bearings / results");
   const int64_t total = offsets[n_pairs];
@@ -147,10 +141,7 @@ extern "C" int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const d
                                         const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, double *kernel_ms) {
   if (kernel_ms) *kernel_ms = 0.0;
   OSFM_REQUIRE(ctx, OSFM_E_INVALID, "osfm_relrot_pairs_pixels: null context");
-  {
-    const int rc = check_args(offsets, n_pairs, prm, "osfm_relrot_pairs_pixels");
-    if (rc != OSFM_OK) return rc;
-  }
+  OSFM_TRY(check_args(offsets, n_pairs, prm, "osfm_relrot_pairs_pixels"));
   if (n_pairs == 0) return OSFM_OK;
   OSFM_REQUIRE(p1 && p2 && results && pair_cams && cam_model && cam_params && n_cams > 0, OSFM_E_INVALID,
                "osfm_relrot_pairs_pixels: null argument");
