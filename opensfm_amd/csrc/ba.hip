@@ -14,6 +14,9 @@
 //     point-major gather + shot-major segmented reduce; no atomics, bit-reproducible);
 //   * all CG scalars stay on the device; the host only polls the residual every few iterations.
 // Every kernel here is HBM-bandwidth bound (gather/scatter + streaming), see DESIGN.md.
+#ifdef OSFM_HIPEMU
+#include <cassert>  // (the host emulation of the tests: the reductions assert their launch size)
+#endif
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -158,9 +161,16 @@ __device__ __forceinline__ void loss_eval(int loss, double a, double s, double &
   }
 }
 
-// block-wide sum of NV values per thread; result valid on thread 0
-template <int NV>
-__device__ __forceinline__ void block_sum(double *v, double *lds /* [4*NV] */) {
+// block-wide sum of NV values per thread, wavefront by wavefront in a fixed order; result valid on thread 0.
+// lds holds NV doubles per wavefront of the workgroup.  MAXT = the most threads the kernel is launched with: its __launch_bounds__, or 1 024
+// (the most a launch can ask for) where it has none -- the array's length is checked against it here, at compile time
+template <int NV, int MAXT, int N>
+__device__ __forceinline__ void block_sum(double *v, double (&lds)[N]) {
+  static_assert(MAXT % 64 == 0 && MAXT <= 1024, "MAXT: the kernel's launch bound, whole wavefronts");
+  static_assert(N >= NV * (MAXT / 64), "block_sum: lds is shorter than NV doubles for every wavefront the launch bound allows");
+#ifdef OSFM_HIPEMU
+  assert((int)blockDim.x <= MAXT);
+#endif
 #pragma unroll
   for (int k = 0; k < NV; k++)
 #pragma unroll
@@ -184,8 +194,12 @@ __device__ __forceinline__ void block_sum(double *v, double *lds /* [4*NV] */) {
 // Sum of NV values per thread over a workgroup of W wavefronts, wavefront by wavefront in a fixed order; the result is valid on thread 0.
 // (the per-shot kernels: one wavefront per shot when there are thousands of shots, W = 4 when there are few -- a 48-shot local bundle
 // adjustment gave 48 wavefronts a thirteen-step loop of ~500 fp64 instructions each and left the other 1 000 SIMDs idle)
-template <int NV, int W>
-__device__ __forceinline__ void shot_sum(double (&v)[NV], double *lds /* [W * NV] when W > 1 */) {
+template <int NV, int W, int N>
+__device__ __forceinline__ void shot_sum(double (&v)[NV], double (&lds)[N] /* W * NV doubles when W > 1 */) {
+  static_assert(W == 1 || N >= W * NV, "shot_sum: lds is shorter than NV doubles per wavefront");
+#ifdef OSFM_HIPEMU
+  assert((int)blockDim.x == 64 * W);
+#endif
 #pragma unroll
   for (int i = 0; i < NV; i++)
 #pragma unroll
@@ -496,7 +510,7 @@ __global__ void __launch_bounds__(kCoopObs) eval_kernel(Dev d, const double *cam
     }
     // the rows are stored LAST, behind the exchange through LDS and the cost's block sum: a barrier behind 26 (+ 9) stores in flight makes every
     // wavefront wait for their acknowledgement (the first version of this kernel: 0.52 ms at configs[4], as much as the two kernels it merged)
-    block_sum<2>(acc, lds);  // (four wavefronts: its barrier also publishes the products)
+    block_sum<2, kCoopObs>(acc, lds);  // (four wavefronts: its barrier also publishes the products)
     if (tid == 0) {
       d.partial[2 * blockIdx.x] = acc[0];
       d.partial[2 * blockIdx.x + 1] = acc[1];
@@ -545,7 +559,7 @@ __global__ void __launch_bounds__(kCoopObs) eval_kernel(Dev d, const double *cam
     }
   }
   __syncthreads();
-  block_sum<2>(acc, lds);
+  block_sum<2, kCoopObs>(acc, lds);
   if (tid == 0) {
     d.partial[2 * blockIdx.x] = acc[0];
     d.partial[2 * blockIdx.x + 1] = acc[1];
@@ -558,7 +572,7 @@ __global__ void finish_reduce_kernel(const double *partial, long n, int ncomp, d
   for (int c = 0; c < ncomp; c++) {
     double v[1] = {0.0};
     for (long i = threadIdx.x; i < n; i += blockDim.x) v[0] += partial[i * ncomp + c];
-    block_sum<1>(v, lds);
+    block_sum<1, 1024>(v, lds);
     if (threadIdx.x == 0) out[c] = v[0];
     __syncthreads();
   }
@@ -589,7 +603,7 @@ __global__ void __launch_bounds__(1024) prior_cost_kernel(Dev d, const double *c
   for (int c = 0; c < 2; c++) {
     double v[1] = {0.0};
     for (long i = threadIdx.x; i < npart; i += blockDim.x) v[0] += partial[i * 2 + c];
-    block_sum<1>(v, lds);
+    block_sum<1, 1024>(v, lds);
     if (threadIdx.x == 0) out[c] = v[0];
     __syncthreads();
   }
@@ -626,7 +640,7 @@ __global__ void __launch_bounds__(1024) prior_cost_kernel(Dev d, const double *c
         for (int i = 0; i < 9; i++) d.up_J[9 * s + i] = wt * J[i];
       }
     }
-  block_sum<1>(v, lds);
+  block_sum<1, 1024>(v, lds);
   if (threadIdx.x == 0) out[0] += v[0];
 }
 
@@ -757,7 +771,7 @@ __global__ void __launch_bounds__(kCamRedT) cam_reduce_kernel(Dev d, int ncomp, 
 #pragma unroll
         for (int i = 0; i < 9; i++) v[i] += p[u][i];
   }
-  block_sum<9>(v, lds);
+  block_sum<9, kCamRedT>(v, lds);
   if (threadIdx.x == 0) {
     for (int i = 0; i < ncomp; i++) d.camred[9 * c + i] = v[i];
     if (grad_cams) cam_grad_one(d, grad_cams, c, v);  // (ncomp = 9: the gradient kernel's sums; one launch less per linearisation)
@@ -3180,7 +3194,7 @@ __global__ void __launch_bounds__(kCoopObs) schur_point_coop_kernel(Dev d, const
         acc[0] = -(m0 * (JA(o, 0) + 0.5 * m0) + m1 * (JA(o, 1) + 0.5 * m1));
       }
       __syncthreads();
-      block_sum<1>(acc, gsum);
+      block_sum<1, kCoopObs>(acc, gsum);
       if (tid == 0) d.partial[blockIdx.x] = acc[0];
       return;
     }
@@ -3233,7 +3247,7 @@ __global__ void __launch_bounds__(kCoopObs) schur_point_coop_kernel(Dev d, const
       acc[0] += -(m0 * (JA(o, 0) + 0.5 * m0) + m1 * (JA(o, 1) + 0.5 * m1));
     }
     __syncthreads();
-    block_sum<1>(acc, gsum);
+    block_sum<1, kCoopObs>(acc, gsum);
     if (tid == 0) d.partial[blockIdx.x] = acc[0];
     return;
   }
@@ -3308,7 +3322,7 @@ __global__ void __launch_bounds__(TPB) schur_finish_kernel(Dev d, const double *
         if (d.shot_camera[s] == c)
 #pragma unroll
           for (int k = 0; k < 3; k++) v[k] += d.part[9 * (long)s + k];
-    block_sum<3>(v, lds);
+    block_sum<3, TPB>(v, lds);
     __syncthreads();
     if (threadIdx.x == 0)
       for (int k = 0; k < 3; k++) {
@@ -3321,7 +3335,7 @@ __global__ void __launch_bounds__(TPB) schur_finish_kernel(Dev d, const double *
       }
   }
   if (mode == 0 && dot_part) {
-    block_sum<1>(dot, lds);
+    block_sum<1, TPB>(dot, lds);
     if (threadIdx.x == 0) dot_part[blockIdx.x] = dot[0];
   }
 }
@@ -3336,7 +3350,7 @@ __global__ void dot2_kernel(const double *a, const double *b, const double *c, c
     v[0] += a[i] * b[i];
     if (c) v[1] += c[i] * e[i];
   }
-  block_sum<2>(v, lds);
+  block_sum<2, 1024>(v, lds);
   if (threadIdx.x == 0) {
     *o0 = v[0];
     if (c) *o1 = v[1];
@@ -3357,7 +3371,7 @@ __global__ void pcg_init_kernel(const double *b, const double *z, double *x, dou
     v[0] += bi * zi;
     v[1] += bi * bi;
   }
-  block_sum<2>(v, lds);
+  block_sum<2, 1024>(v, lds);
   if (threadIdx.x == 0) {
     *o_rz = v[0];
     *o_bb = v[1];
@@ -3377,7 +3391,7 @@ __global__ void __launch_bounds__(TPB) pcg_step1_kernel(double *x, double *r, co
     if (dot_part) {
       double a[1] = {0.0};
       for (int q = threadIdx.x; q < nparts; q += TPB) a[0] += dot_part[q];
-      block_sum<1>(a, lds);
+      block_sum<1, TPB>(a, lds);
       pAp = a[0];
     } else
       pAp = *o_pAp;
@@ -3397,7 +3411,7 @@ __global__ void __launch_bounds__(TPB) pcg_step1_kernel(double *x, double *r, co
     r[i] = ri;
     v[0] = ri * ri;
   }
-  block_sum<1>(v, lds);
+  block_sum<1, TPB>(v, lds);
   if (threadIdx.x == 0) rr_part[blockIdx.x] = v[0];
 }
 __global__ void precond_apply_kernel(Dev d, const double *r, double *z) {
@@ -3435,18 +3449,18 @@ __global__ void pcg_step2_kernel(double *p, const double *z, int n, const double
 // finish_reduce_kernel's and shot_rot_kernel's launches behind this one are gone)
 __global__ void __launch_bounds__(1024) candidate_kernel(Dev d, const double *y, const double *partial, long npart, double *out, const double *part2, long npart2,
                                                          double *out2, int do_rot) {
-  __shared__ double lds[32];
+  __shared__ double lds[16 * 3];  // (sixteen wavefronts, three sums)
   {
     double m[1] = {0.0};
     for (long i = threadIdx.x; i < npart; i += blockDim.x) m[0] += partial[i];
-    block_sum<1>(m, lds);
+    block_sum<1, 1024>(m, lds);
     if (threadIdx.x == 0) out[0] = m[0];
     __syncthreads();
   }
   for (int c = 0; c < 2; c++) {
     double m[1] = {0.0};
     for (long i = threadIdx.x; i < npart2; i += blockDim.x) m[0] += part2[2 * i + c];
-    block_sum<1>(m, lds);
+    block_sum<1, 1024>(m, lds);
     if (threadIdx.x == 0) out2[c] = m[0];
     __syncthreads();
   }
@@ -3516,7 +3530,7 @@ __global__ void __launch_bounds__(1024) candidate_kernel(Dev d, const double *y,
     // one workgroup were 67 us at configs[4] against the 6 us of the launch
     if (do_rot) rot_and_derivs(pn, d.shotR + 36 * (long)s, d.shotR + 36 * (long)s + 9);
   }
-  block_sum<3>(v, lds);
+  block_sum<3, 1024>(v, lds);
   if (threadIdx.x == 0) {
     out[0] += v[0];
     out[1] = v[1];
@@ -3536,7 +3550,7 @@ __global__ void __launch_bounds__(TPB) candidate_points_kernel(Dev d, double *pa
       v[1] = d.pts[i] * d.pts[i];
     }
   }
-  block_sum<2>(v, lds);
+  block_sum<2, TPB>(v, lds);
   if (threadIdx.x == 0) {
     part[2 * blockIdx.x] = v[0];
     part[2 * blockIdx.x + 1] = v[1];
@@ -3613,7 +3627,7 @@ __global__ void border_dots_kernel(const double *Bc, const double *W, int nb, in
   double v[1] = {0.0};
 #pragma unroll 4
   for (int t = threadIdx.x; t < n; t += blockDim.x) v[0] += Bc[(long)i * n + t] * W[(long)j * n + t];
-  block_sum<1>(v, lds);
+  block_sum<1, 1024>(v, lds);
   if (threadIdx.x == 0) out[blockIdx.x] = v[0];
 }
 // z_c = SigInv (r_c - B^T z_s)   (single block)
@@ -3623,7 +3637,7 @@ __global__ void border_rhs_kernel(const double *Bc, const double *SigInv, const 
   for (int i = 0; i < nb; i++) {  // (all rows in one pass over z_s with six accumulators was measured in round 4: 37 against 33 us)
     double v[1] = {0.0};
     for (int t = threadIdx.x; t < n; t += blockDim.x) v[0] += Bc[(long)i * n + t] * z[t];
-    block_sum<1>(v, lds);
+    block_sum<1, 1024>(v, lds);
     if (threadIdx.x == 0) y[i] = r[cam0 + i] - v[0];
     __syncthreads();
   }
@@ -3641,7 +3655,7 @@ __global__ void __launch_bounds__(1024) border_rhs_dots_kernel(const double *Bc,
   const int i = blockIdx.x;
   double v[1] = {0.0};
   for (int t = threadIdx.x; t < n; t += blockDim.x) v[0] += Bc[(long)i * n + t] * z[t];
-  block_sum<1>(v, lds);
+  block_sum<1, 1024>(v, lds);
   if (threadIdx.x == 0) y[i] = r[cam0 + i] - v[0];
 }
 __global__ void border_rhs_apply_kernel(const double *SigInv, const double *y, double *z, int nb, int cam0) {
@@ -3893,7 +3907,7 @@ __global__ void __launch_bounds__(TPB) border_cam_kernel(Dev d, const double *pa
     if (d.shot_camera[s] == cam)
 #pragma unroll
       for (int i = 0; i < 3 * NB; i++) v[i] += partB[(long)s * 3 * NB + i];
-  block_sum<3 * NB>(v, lds);
+  block_sum<3 * NB, TPB>(v, lds);
   if (threadIdx.x == 0)
     for (int c = 0; c < NB; c++)
       for (int k = 0; k < 3; k++) {

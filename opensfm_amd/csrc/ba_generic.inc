@@ -247,7 +247,7 @@ __global__ void __launch_bounds__(TPB) gen_eval_kernel(Dev d, const double *cam,
       }
     }
   }
-  block_sum<2>(acc, lds);
+  block_sum<2, TPB>(acc, lds);
   if (threadIdx.x == 0) {
     d.partial[2 * blockIdx.x] = acc[0];
     d.partial[2 * blockIdx.x + 1] = acc[1];
@@ -922,7 +922,7 @@ __global__ void __launch_bounds__(256) gen_border_reduce_kernel(Dev d, int strid
     const int slot = g.col_slot[(long)j * g.NV + vw];
     if (slot != 255) v[0] += g.vpart[(long)vw * stride + off + slot];
   }
-  block_sum<1>(v, lds);
+  block_sum<1, 256>(v, lds);
   if (threadIdx.x == 0) {
     const int i = d.cam0 + j;
     if (mode == 0) d.zc[i] = v[0];
@@ -1061,7 +1061,7 @@ __global__ void __launch_bounds__(kCoopObs) gen_schur_point_kernel(Dev d, const 
         }
       }
       __syncthreads();
-      block_sum<1>(acc, gsum);
+      block_sum<1, kCoopObs>(acc, gsum);
       if (tid == 0) d.partial[blockIdx.x] = acc[0];
       return;
     }
@@ -1118,7 +1118,7 @@ __global__ void __launch_bounds__(kCoopObs) gen_schur_point_kernel(Dev d, const 
       }
     }
     __syncthreads();
-    block_sum<1>(acc, gsum);
+    block_sum<1, kCoopObs>(acc, gsum);
     if (tid == 0) d.partial[blockIdx.x] = acc[0];
     return;
   }
@@ -1184,7 +1184,7 @@ __global__ void __launch_bounds__(256) gen_bpri_dot_kernel(Dev d, const double *
   const int per = (n6 + kBpriSlices - 1) / kBpriSlices, t0 = c * per, t1 = min(n6, t0 + per);
   double v[1] = {0.0};
   for (int t = t0 + threadIdx.x; t < t1; t += 256) v[0] += g.Bpri[(long)j * n6 + t] * y[t];
-  block_sum<1>(v, lds);
+  block_sum<1, 256>(v, lds);
   if (threadIdx.x == 0) g.bdot[j * kBpriSlices + c] = v[0];
 }
 
@@ -1223,7 +1223,7 @@ __global__ void __launch_bounds__(TPB) gen_schur_finish_kernel(Dev d, const doub
   double dot[1] = {0.0};
   if (i < d.nred) dot[0] = gen_schur_finish_row(d, x, y, out, radius, mode, have_obs, have_bpri, i, mode == 0 && dot_part != nullptr);
   if (mode == 0 && dot_part) {
-    block_sum<1>(dot, lds);
+    block_sum<1, TPB>(dot, lds);
     if (threadIdx.x == 0) dot_part[blockIdx.x] = dot[0];
   }
 }
@@ -1358,7 +1358,7 @@ __global__ void gen_candidate_kernel(Dev d, const double *y, double *out) {
     upd(g.bias + 7 * c, g.bias_n + 7 * c, 7, g.bias_col[c] < 0 ? -1 : n6 + g.bias_col[c]);
   }
   for (int q = threadIdx.x; q < g.NRC; q += blockDim.x) upd(g.rc + 6 * q, g.rc_n + 6 * q, 6, g.rc_col[q] < 0 ? -1 : n6 + g.rc_col[q]);
-  block_sum<2>(v, lds);
+  block_sum<2, 1024>(v, lds);
   if (threadIdx.x == 0) {
     out[1] = v[0];
     out[2] = v[1];
@@ -1421,7 +1421,7 @@ __global__ void gen_border_rhs_kernel(const double *Bc, const double *SigInv, co
   for (int i = 0; i < nb; i++) {
     double v[1] = {0.0};
     for (int t = threadIdx.x; t < n; t += blockDim.x) v[0] += Bc[(long)i * n + t] * z[t];
-    block_sum<1>(v, lds);
+    block_sum<1, 1024>(v, lds);
     if (threadIdx.x == 0) yy[i] = r[cam0 + i] - v[0];
     __syncthreads();
   }
@@ -1669,7 +1669,7 @@ __global__ void __launch_bounds__(256) gen_border_finish_kernel(Dev d, const int
         const int slot = g.col_slot[(long)row * g.NV + vw];
         if (slot != 255) v[0] += vpartB[((long)vw * ncols + c) * g.KW + slot];
       }
-    block_sum<1>(v, lds);
+    block_sum<1, 256>(v, lds);
     if (threadIdx.x == 0) {
       const double sr = d.sc_red[n6 + row], scol = d.sc_red[n6 + col];
       Cm[row * NB + col] = sr * (v[0] + g.Cpri[(long)row * NB + col] * scol) + (row == col ? d.D_red[n6 + row] / radius : 0.0);

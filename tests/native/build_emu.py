@@ -27,6 +27,16 @@ def transform(text: str) -> str:
     return text
 
 
+def asan_runtime():
+    """the shared AddressSanitizer runtime of the compiler that builds the sanitized library (a process that loads that library needs it
+    in LD_PRELOAD), or None when the toolchain has none"""
+    try:
+        path = subprocess.run([CLANG, "-print-file-name=libclang_rt.asan-x86_64.so"], capture_output=True, text=True).stdout.strip()
+    except OSError:
+        return None
+    return path if os.path.isabs(path) and os.path.exists(path) else None
+
+
 def build(force: bool = False, sanitize: bool = False) -> str:
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, "libosfm_ba_emu_asan.so" if sanitize else "libosfm_ba_emu.so")
@@ -38,7 +48,9 @@ def build(force: bool = False, sanitize: bool = False) -> str:
         return so
     flags = ["-std=c++17", "-fPIC", "-ffp-contract=off", "-DOSFM_HIPEMU", "-Wno-unknown-attributes", "-Wno-unused-value", "-I", os.path.join(HERE, "hipemu"), "-I", CSRC,
              "-I", os.path.join(ROOT, "include")]
-    flags += ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]
+    # sanitized: -O0 and line tables only.  The optimiser's passes over the instrumented kernels were nearly all of the build's time (one translation unit:
+    # over ten minutes at -O1, with -g or with line tables alone; under twenty seconds at -O0), and a report needs no more than file and line.
+    flags += ["-O0", "-gline-tables-only", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DHIPEMU_STACK_BYTES=(128*1024)"] if sanitize else ["-O2"]
     objs = []
     procs = []
     for inc in os.listdir(CSRC):  # the .inc files the sources include get the same substitutions (found first: next to the generated sources)

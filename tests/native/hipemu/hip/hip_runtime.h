@@ -151,7 +151,10 @@ struct Lane {
   uint64_t post, result;
   double ma, mb, mc[4], md[4];
 };
-constexpr size_t kStackBytes = 512 * 1024;
+#ifndef HIPEMU_STACK_BYTES
+#define HIPEMU_STACK_BYTES (512 * 1024)
+#endif
+constexpr size_t kStackBytes = HIPEMU_STACK_BYTES;  // per fibre (AddressSanitizer clears a fibre's whole stack shadow at every switch to it: its build asks for less)
 constexpr int kMaxThreads = 1024;
 inline Lane *g_lanes = nullptr;
 inline char *g_stacks = nullptr;

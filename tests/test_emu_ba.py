@@ -32,6 +32,24 @@ def test_streaming_solver_narrow_band_matches_oracle(oracle_lib):
     assert abs(_rmse_px(g["reproj_err"]) - _rmse_px(o["reproj_err"])) < 1e-4
 
 
+def test_one_wavefront_per_shot_beyond_1024_shots_matches_oracle(oracle_lib):
+    """1 025 shots, one past kShotWavesBelow: shot_grad_kernel<1>, schur_shot_kernel<1> and border_shot_kernel<3, 1> (shot_sum without its LDS
+    stage), the candidate's rotation blocks from shot_rot_kernel's launch instead of candidate_kernel, and the second trip of the strided
+    loops of candidate_kernel and prior_cost_kernel, whose reductions now carry values in all sixteen wavefronts -- a minute and a half on
+    the emulation.  (1 024 shots, the other side of the switch, run four wavefronts per shot on the emulation: over five minutes; the GPU
+    suite has both sides.)"""
+    from opensfm_amd import bundle
+
+    pr = synthetic.make_ba_scene(1025, 4100, 4, seed=5)
+    with emulated():
+        g = bundle.bundle_arrays(pr, {"bundle_max_iterations": 3}, **NO_TOL)
+    o = oracle_lib.ba_solve(pr, max_iterations=3, **NO_TOL)
+    assert g["iterations"] == o["iterations"] == 3 and g["successful_steps"] == o["successful_steps"]
+    assert np.allclose(g["cost_history"], o["cost_history"], rtol=1e-10), (g["cost_history"], o["cost_history"])
+    assert abs(_rmse_px(g["reproj_err"]) - _rmse_px(o["reproj_err"])) < 1e-4
+    assert np.abs(g["shot_pose"] - o["shot_pose"]).max() < 1e-8
+
+
 def _compare_general(oracle_lib, pr, iters=5, rtol=1e-9):
     from opensfm_amd import bundle
 

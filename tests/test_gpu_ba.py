@@ -532,3 +532,114 @@ def test_results_do_not_depend_on_what_the_cached_slabs_held(gpu_ctx):
                     assert np.array_equal(g[k], f[k]), (rep, k)
     finally:
         shared.close()
+
+
+# ---- more than kShotWavesBelow = 1 024 shots ------------------------------------------------------------------------------------------------
+# The per-shot kernels run four wavefronts per shot up to 1 024 shots and one beyond (shot_grad_kernel, schur_shot_kernel, border_shot_kernel:
+# the other branch of shot_sum); beyond 1 024 the candidate's rotation blocks come from shot_rot_kernel instead of candidate_kernel; and the
+# single-workgroup kernels of 1 024 threads (candidate_kernel, prior_cost_kernel) take the second trip of their strided loops over the shots.
+# Scenes: a few points per shot, tracks of four -- the oracle solves each in well under a second.
+_ORACLE_CACHE = {}
+
+
+def _oracle_once(oracle_lib, key, problem, **kw):
+    """one oracle solve per (scene, options), shared by the tests below; the result is not modified"""
+    if key not in _ORACLE_CACHE:
+        _ORACLE_CACHE[key] = oracle_lib.ba_solve(problem, **kw)
+    return _ORACLE_CACHE[key]
+
+
+def _scene_with_every_prior(S=1100):
+    """GPS priors with a small sigma on all shots (the prior part of the model change matters), up vectors on most, every fifth shot
+    constant, two cameras of which one is constant: every branch candidate_kernel and prior_cost_kernel take per shot and per camera, also in
+    the threads beyond 640 (wavefronts 10 .. 15 of their reductions)"""
+    key = ("every_prior", S)
+    if key not in _ORACLE_CACHE:
+        pr = synthetic.make_ba_scene(S, 4 * S, 4, seed=5, gps_sigma=0.05)
+        pr["shot_up"] = np.tile([0.0, -2.0, 0.0], (S, 1))
+        pr["shot_up_sigma"] = np.full(S, 1e-3)
+        pr["shot_up_sigma"][::7] = 0.0
+        pr["shot_fixed"] = (np.arange(S) % 5 == 0).astype(np.uint8)
+        base = pr["cam_params"][0]
+        pr["cam_params"] = np.array([base, base * [1.1, 0.9, 1.02]])
+        pr["cam_prior"] = np.tile(pr["cam_prior"][0], (2, 1))
+        pr["cam_sigma"] = np.tile(pr["cam_sigma"][0], (2, 1))
+        pr["cam_fixed"] = np.array([0, 1], np.uint8)
+        pr["shot_camera"] = (np.arange(S) % 2).astype(np.int32)
+        _ORACLE_CACHE[key] = pr
+    return _ORACLE_CACHE[key]
+
+
+def _assert_trajectory(g, o, iters):
+    assert g["iterations"] == o["iterations"] == iters
+    assert g["successful_steps"] == o["successful_steps"]
+    assert np.allclose(g["cost_history"], o["cost_history"], rtol=1e-7), (g["cost_history"], o["cost_history"])
+    assert abs(_rmse_px(g["reproj_err"]) - _rmse_px(o["reproj_err"])) < 1e-4
+    assert np.allclose(g["shot_pose"], o["shot_pose"], atol=1e-5)
+    assert np.allclose(g["cam_params"], o["cam_params"], atol=1e-6)
+
+
+@pytest.mark.parametrize("shots", [1024, 1025, 1100])
+def test_shot_count_boundary_matches_oracle(oracle_lib, gpu_ctx, shots):
+    """1 024 and 1 025 shots sit on either side of every switch on the shot count; 1 100 leaves the second trip of the strided loops a
+    wavefront and a bit"""
+    from opensfm_amd import bundle
+
+    pr = synthetic.make_ba_scene(shots, 4 * shots, 4, seed=5)
+    g = bundle.bundle_arrays(pr, {"bundle_max_iterations": 10}, **NO_TOL)
+    o = _oracle_once(oracle_lib, ("boundary", shots), pr, max_iterations=10, **NO_TOL)
+    _assert_trajectory(g, o, 10)
+    assert g["preconditioner_bandwidth"] == g["shot_bandwidth"] == 3
+
+
+def test_every_prior_and_constant_blocks_beyond_1024_shots(oracle_lib, gpu_ctx):
+    from opensfm_amd import bundle
+
+    pr = _scene_with_every_prior()
+    g = bundle.bundle_arrays(pr, {"bundle_max_iterations": 10}, **NO_TOL)
+    o = _oracle_once(oracle_lib, "every_prior_10", pr, max_iterations=10, **NO_TOL)
+    _assert_trajectory(g, o, 10)
+    assert np.array_equal(g["shot_pose"][::5], pr["shot_pose"][::5]) and np.array_equal(g["cam_params"][1], pr["cam_params"][1])
+    assert np.abs(g["shot_pose"][1::5] - pr["shot_pose"][1::5]).max() > 0 and np.abs(g["cam_params"][0] - pr["cam_params"][0]).max() > 0
+
+
+def test_parameter_tolerance_stop_beyond_1024_shots(oracle_lib, gpu_ctx):
+    """the stop on the parameter tolerance compares candidate_kernel's two norms, |step| and |x| over the variable blocks; the shots beyond
+    640 reach them through wavefronts 10 .. 15 of its reduction.  The oracle stops after 2 iterations at 1e-3, and also at 5e-4 and at
+    2e-3 (4 iterations at 1e-4): the stop does not sit on a rounding edge"""
+    from opensfm_amd import bundle
+
+    pr = _scene_with_every_prior()
+    tol = dict(function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=1e-3)
+    g = bundle.bundle_arrays(pr, {}, **tol)
+    o = _oracle_once(oracle_lib, "every_prior_ptol", pr, **tol)
+    assert g["termination"] == o["termination"] == 3
+    assert o["iterations"] == 2 and abs(g["iterations"] - o["iterations"]) <= 1
+    n = min(len(g["cost_history"]), len(o["cost_history"]))
+    assert np.allclose(g["cost_history"][:n], o["cost_history"][:n], rtol=1e-7)
+
+
+def test_two_solves_beyond_1024_shots_are_bit_equal(gpu_ctx):
+    """every reduction of the [k1 k2 focal] path is in a fixed order: two solves in one process give the same bits"""
+    from opensfm_amd import bundle
+
+    pr = _scene_with_every_prior()
+    a = bundle.bundle_arrays(pr, {"bundle_max_iterations": 6}, **NO_TOL)
+    b = bundle.bundle_arrays(pr, {"bundle_max_iterations": 6}, **NO_TOL)
+    for k in ("cost_history", "shot_pose", "points", "cam_params"):
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_local_problem_with_more_than_1024_interior_shots(oracle_lib, gpu_ctx):
+    """BundleLocal's problem grown to 1 100 interior shots (constant cameras: inert camera rows, no border; the band alone is the reduced
+    matrix) with its constant boundary shots at both ends"""
+    from opensfm_amd import bundle
+
+    pr = synthetic.make_ba_scene(1300, 5200, 4, seed=5)
+    sub = bundle.local_problem(pr, 650, {"local_bundle_radius": 1000, "local_bundle_min_common_points": 1, "local_bundle_max_shots": 1100})[0]
+    assert sub["cam_fixed"].all() and (sub["shot_fixed"] == 0).sum() == 1100 and (sub["shot_fixed"] == 1).sum() > 0
+    g = bundle.bundle_arrays(sub, {"bundle_max_iterations": 6}, **NO_TOL)
+    o = oracle_lib.ba_solve(sub, max_iterations=6, **NO_TOL)
+    _assert_trajectory(g, o, 6)
+    assert np.array_equal(g["shot_pose"][sub["shot_fixed"] == 1], sub["shot_pose"][sub["shot_fixed"] == 1])
+    assert g["pcg_iterations"] <= 2 * g["iterations"]

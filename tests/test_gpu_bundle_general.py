@@ -163,6 +163,28 @@ def test_brown_camera_free_bias_control_points_at_scale(oracle_lib, gpu_ctx, rag
     assert g["preconditioner_bandwidth"] == g["shot_bandwidth"] and (g["shot_bandwidth"] > 10) == ragged
 
 
+def test_brown_camera_free_bias_control_points_beyond_1024_shots(oracle_lib, gpu_ctx):
+    """1 100 rig instances: gen_candidate_kernel and finish_reduce_kernel are single workgroups of 1 024 threads that walk the instances and
+    the partial sums with that stride -- their second trip runs only beyond 1 024 (gen_candidate_kernel's block_sum<2> fills its LDS array
+    exactly at sixteen wavefronts).  A BROWN camera with nine free intrinsics, position priors through a free similarity bias, control
+    points; a few points per shot and tracks of four keep the oracle's reduced system (6 616 unknowns, a band and sixteen border rows) cheap"""
+    from opensfm_amd import bundle
+
+    pr = synthetic.make_general_ba_scene(1100, 4400, 4, model="brown", n_gcp=5, gps_bias=True, seed=5)
+    assert len(pr["rig_instance_pose"]) == 1100
+    g = bundle.bundle_general_arrays(pr, {"bundle_max_iterations": 6}, ctx=gpu_ctx, **NO_TOL)
+    o = oracle_lib.bundle_general(pr, max_iterations=6, **NO_TOL)
+    assert g["iterations"] == o["iterations"] == 6
+    assert g["successful_steps"] == o["successful_steps"]
+    assert np.allclose(g["cost_history"], o["cost_history"], rtol=1e-7), (g["cost_history"], o["cost_history"])
+    assert abs(_rmse_px(g["reproj_err"][:, :2]) - _rmse_px(o["reproj_err"][:, :2])) < 1e-4
+    for k in ("cam_params", "rig_instance_pose", "points", "bias"):
+        assert np.allclose(g[k], o[k], atol=1e-6), k
+    assert g["final_cost"] < g["initial_cost"]
+    assert np.abs(g["bias"][0] - pr["bias"][0]).max() > 1e-3 and np.abs(g["cam_params"][0, :9] - pr["cam_params"][0, :9]).max() > 0
+    assert g["preconditioner_bandwidth"] == g["shot_bandwidth"]
+
+
 def test_brown_camera_at_configs2_size_twenty_iterations(oracle_lib, gpu_ctx):
     """BASELINE configs[2] (500 cams / 50 k points / 300 k observations, 20 LM iterations) with what BAHelpers::Bundle builds on a calibrated
     data set: a BROWN camera with nine free intrinsics and their priors, GPS priors through a free similarity bias, 20 control points.
