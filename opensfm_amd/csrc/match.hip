@@ -20,6 +20,7 @@
 // keys 0.39 of the int8 peak, profiles/r01_*, r02_bench_mid.json -- were removed; the exact VALU kernel below remains as the
 // on-GPU cross-check.)
 #include <cstdlib>
+#include <type_traits>
 
 #include "osfm_internal.h"
 
@@ -156,6 +157,15 @@ __device__ __forceinline__ int dot_rows8(const int8_t *tilesA, int rowA, const i
   return s0 + s1;
 }
 
+// a wave-uniform pointer, as the scalar registers the compiler does not always grant it: loads through it take the
+// scalar-base + 32-bit lane offset form (no 64-bit address per lane to build, keep or spill)
+template <class P>
+__device__ __forceinline__ P *uniform_ptr(P *p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (P *)(((unsigned long long)hi << 32) | lo);
+}
+
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
@@ -243,19 +253,22 @@ struct QueryPassShared {
 };
 
 // queries: slot q in [0, nslots) is feature qsel[q] of image Q (qsel == nullptr: identity); targets: all nT features of image T.
-// out[query feature] = its nearest target if the ratio test passes, else kNone.  Returns the collision flag.
+// out[query feature] = its nearest target if the ratio test passes, else kNone.  Returns the collision flag; any_hit = whether any
+// query of the pass got a target (workgroup-uniform: the OR goes through *hit_word, an LDS word that is zero on entry, across the
+// pass's closing barrier.  Not __syncthreads_or: the library's workgroup reduction brings static LDS of its own, and the kernel
+// already asks for the whole 160 KiB as dynamic LDS).
 template <bool GATHER, bool FQ>
 __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_t *tilesQ, const int32_t *normQ, int nQ, int nslots,
                                           const unsigned short *qsel, const int8_t *tilesT, const int32_t *normT, const int32_t *hnegT,
                                           int nT, const int8_t *tiles_pad, const int32_t *hneg_pad, unsigned short *out, double ratio,
-                                          int tid, const float *descQ, const float *descT, double eps) {
+                                          int tid, const float *descQ, const float *descT, double eps, int *hit_word, int &any_hit) {
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tT = (nT + 31) >> 5;
   const int tS = (nslots + 31) >> 5;
   const int nchunks = (tS + kCT4 - 1) / kCT4;
   const int nrb = (tT + kWaves * kRT - 1) / (kWaves * kRT);
-  int flag = 0;
+  int flag = 0, hit = 0;
 
   // one chunk = 8 query tiles, global -> LDS by DMA; thread (w, lane) moves bytes [w*1024 + lane*16, +16) of every tile, i.e. the
   // K slice w of feature (lane & 31), half (lane >> 5) -- which is also how a gathered query is addressed
@@ -282,34 +295,41 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
   //   A operands: global -> VGPR, one step ahead, into the register set the running step does not use;
   //   accumulator seeds: global -> LDS by DMA (each wave stages the 64 seeds of its own two row tiles, so only its own vmcnt
   //   orders them), read into the seed tuples as soon as the running step has issued its last seeded MFMA.
+  // A full step issues the three parts in the gaps of its own first tile, a partial one ahead of itself.
+  auto load_seeds = [&](int rb, int slot) {
+    const int t = rb * (kWaves * kRT) + w * kRT;  // wave-uniform: the halves of the wave stage one row tile each
+    const int32_t *h0 = uniform_ptr((t < tT) ? hnegT + (long)t * 32 : hneg_pad);
+    const int32_t *h1 = uniform_ptr((t + 1 < tT) ? hnegT + (long)(t + 1) * 32 : hneg_pad);
+    const int32_t *hp = ((lane >> 5) ? h1 : h0) + (lane & 31);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)hp,
+                                     (__attribute__((address_space(3))) void *)(sh.hbuf + slot * 256 + w * 64), 4, 0, 0);
+  };
+  auto load_rows = [&](int rb, v4i (&af)[kRT][4], int rt) {
+    const int t = rb * (kWaves * kRT) + w * kRT + rt;  // wave-uniform
+    const auto *tp = (const __attribute__((address_space(1))) int8_t *)uniform_ptr((t < tT) ? tilesT + (long)t * OSFM_TILE_BYTES : tiles_pad);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) af[rt][ks] = *(const __attribute__((address_space(1))) v4i *)(tp + ks * 1024 + lane * 16);
+  };
   auto load_targets = [&](int rb, v4i (&af)[kRT][4], int slot) {
-    {
-      const int t = rb * (kWaves * kRT) + w * kRT + (lane >> 5);
-      const int32_t *hp = ((t < tT) ? hnegT + (long)t * 32 : hneg_pad) + (lane & 31);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)hp,
-                                       (__attribute__((address_space(3))) void *)(sh.hbuf + slot * 256 + w * 64), 4, 0, 0);
-    }
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) {
-      const int t = rb * (kWaves * kRT) + w * kRT + rt;  // wave-uniform
-      const int8_t *tp = (t < tT) ? tilesT + (long)t * OSFM_TILE_BYTES : tiles_pad;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) af[rt][ks] = *(const v4i *)(tp + ks * 1024 + lane * 16);
-    }
+    load_seeds(rb, slot);  // the issue order (seeds, row tile 0, row tile 1) is what the vmcnt in the step's last tile counts on
+    load_rows(rb, af, 0);
+    load_rows(rb, af, 1);
   };
   v16i hn[kRT];
   // accumulator register r of half h belongs to row (r & 3) + 8 (r >> 2) + 4 h of the tile
+  auto read_seeds_rt = [&](int slot, int rt) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const v4i hv = *(const v4i *)(sh.hbuf + slot * 256 + w * 64 + rt * 32 + 8 * g + 4 * (lane >> 5));
+      hn[rt][4 * g + 0] = hv[0];
+      hn[rt][4 * g + 1] = hv[1];
+      hn[rt][4 * g + 2] = hv[2];
+      hn[rt][4 * g + 3] = hv[3];
+    }
+  };
   auto read_seeds = [&](int slot) {
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const v4i hv = *(const v4i *)(sh.hbuf + slot * 256 + w * 64 + rt * 32 + 8 * g + 4 * (lane >> 5));
-        hn[rt][4 * g + 0] = hv[0];
-        hn[rt][4 * g + 1] = hv[1];
-        hn[rt][4 * g + 2] = hv[2];
-        hn[rt][4 * g + 3] = hv[3];
-      }
+    read_seeds_rt(slot, 0);
+    read_seeds_rt(slot, 1);
   };
 
   int cb[kCT4], cs[kCT4], ci[kCT4];
@@ -335,15 +355,29 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
   // tile) run interleaved on two of THREE accumulator tuples; the tuples of the previous tile are reduced in the issue gaps of the
   // current one (an in-order wavefront hides about five plain VALU instructions behind a 32-cycle MFMA, MI355X_MICROARCH.md), and the
   // first chain's tuple of tile t-1 becomes the second chain's tuple of tile t.  The class update of tile t-1 rides in the later gaps.
-  auto step = [&](const v4i (&af)[kRT][4], int rb, int next_slot, bool chunk_dma_in_flight) {
+  //
+  // Partial steps run only the tiles that exist, in the same pipeline:
+  //   * a chunk with nt < 8 query tiles (the last one of an image or of the candidate list) ENTERS the unrolled tile sequence at
+  //     t0 = 8 - nt: stage t works on query tile t - t0 (bq = the chunk's base moved back by t0 tiles), so the seed fetch in tile 7
+  //     and the drain are the full step's.  The entry stage reduces whatever the tuples held into cb/cs/ci[t0 - 1], which the merge
+  //     files under query tile 7 of the chunk -- one that does not exist when nt < 8, and whose slots nobody decides;
+  auto step = [&](const v4i (&af)[kRT][4], v4i (&nxt)[kRT][4], int rb, int rbn, int next_slot, int t0, const unsigned char *bq) {
+    const int vrb = rb;  // the class index of this step, in a vector register for the selects below
     v16i T[3];
     int mp = 0;
+    asm volatile("; osfm-step: a step of the sweep begins (tests/test_kernel_budgets_sweep.py)");
 #pragma unroll
     for (int t = 0; t < kCT4; ++t) {
+      if (t == 0 && t0 > 0) {  // a partial step has no first tile to hide the fetch of the next step's targets in
+        load_targets(rbn, nxt, next_slot);
+        continue;
+      }
+      if (t < kCT4 - 1 && t < t0) continue;  // (t0 <= 7: the last stage always runs)
+      // tile 7 prefetches the first tile of the next step
+      const unsigned char *nb = (t == kCT4 - 1 ? bq + t0 * OSFM_TILE_BYTES : bq + (t + 1) * OSFM_TILE_BYTES) + lane * 16;
       v16i &C1 = T[(2 * t) % 3];
       v16i &C2 = T[(2 * t + 1) % 3];      // = chain 1 of tile t-1: reduced in the first gap
       v16i &P2 = T[(2 * t + 2) % 3];      // = chain 2 of tile t-1
-      const unsigned char *nb = bb + ((t + 1) & (kCT4 - 1)) * OSFM_TILE_BYTES + lane * 16;  // tile 7 prefetches tile 0 (next step)
       int a0 = 0, b0 = 0, a1 = 0, b1 = 0, m2 = 0;
       C1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][0], bf[0], hn[0], 0, 0, 0);
       OSFM_PIN
@@ -352,25 +386,25 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
         OSFM_TREE_B(C2, a0, b0)
         OSFM_TREE_C(C2, a0, b0)
         OSFM_TREE_D(C2, a0, b0, mp)
+      } else {
+        load_seeds(rbn, next_slot);  // the next step's targets, in the gaps that have no previous tile to reduce
       }
       OSFM_PIN
       C2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][0], bf[0], hn[1], 0, 0, 0);
       OSFM_PIN
       if (t == kCT4 - 1) {
-        // the step's last seeded MFMAs are out: fetch the next step's seeds.  Their DMA is older than this step's 8 A-operand loads
-        // (and than the 8 DMAs of the next chunk, when those were issued in this step)
-        if (chunk_dma_in_flight)
-          __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * kRT * 4 + kCT4));  // vmcnt(16)
-        else
-          __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * kRT * 4));  // vmcnt(8)
-        read_seeds(next_slot);
+        // the step's last seeded MFMAs are out: fetch the next step's seeds.  Their DMA is older than the 8 A-operand loads this step
+        // issued (and the 8 DMAs of the next chunk, issued ahead of the chunk's first step, are older still)
+        __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * kRT * 4));  // vmcnt(8)
+        read_seeds_rt(next_slot, 0);
       }
       bf[0] = *(const v4i *)(nb);
       if (t > 0) { OSFM_TREE_A(P2, a1, b1) }
       OSFM_PIN
       C1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][1], bf[1], C1, 0, 0, 0);
       OSFM_PIN
-      if (t > 0) { OSFM_TREE_B(P2, a1, b1) }
+      if (t > 0) { OSFM_TREE_B(P2, a1, b1) } else { load_rows(rbn, nxt, 0); }
+      if (t == kCT4 - 1) read_seeds_rt(next_slot, 1);
       OSFM_PIN
       C2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][1], bf[1], C2, 0, 0, 0);
       OSFM_PIN
@@ -379,7 +413,7 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       OSFM_PIN
       C1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][2], bf[2], C1, 0, 0, 0);
       OSFM_PIN
-      if (t > 0) { OSFM_TREE_D(P2, a1, b1, m2) }
+      if (t > 0) { OSFM_TREE_D(P2, a1, b1, m2) } else { load_rows(rbn, nxt, 1); }
       OSFM_PIN
       C2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][2], bf[2], C2, 0, 0, 0);
       OSFM_PIN
@@ -391,7 +425,9 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       OSFM_PIN
       C1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[0][3], bf[3], C1, 0, 0, 0);
       OSFM_PIN
-      if (t > 0) ci[t - 1] = m2 > cb[t - 1] ? rb : ci[t - 1];
+      // (as volatile assembly: left to the compiler, the eight selects of a step all sink into its last tile)
+      if (t > 0)
+        asm volatile("v_cmp_gt_i32 vcc, %1, %2\n\ts_nop 1\n\tv_cndmask_b32 %0, %0, %3, vcc" : "+v"(ci[t - 1]) : "v"(m2), "v"(cb[t - 1]), "v"(vrb) : "vcc");
       OSFM_PIN
       C2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[1][3], bf[3], C2, 0, 0, 0);
       OSFM_PIN
@@ -418,24 +454,32 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
     }
   };
 
+  // the norm of the query a thread decides at the end of chunk c: requested one chunk ahead, so that no chunk waits for it alone
+  auto load_norm = [&](int c) {
+    const int slot = c * kChunkCols4 + tid;
+    const int f = slot < nslots ? (GATHER ? (int)qsel[slot] : slot) : -1;
+    return (f >= 0 && f < nQ) ? normQ[f] : OSFM_PAD_NORM;
+  };
   dma_chunk(0);
   // two register sets for the A operands: the step that computes on one set fetches the next step's targets into the other
   v4i afA[kRT][4], afB[kRT][4];
   load_targets(0, afA, 0);
+  int myna_next = load_norm(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): chunk 0, the first targets and their seeds
   read_seeds(0);
   int sidx = 0;  // global step counter: the seeds of step s are staged in slot s & 1
 
   for (int c = 0; c < nchunks; ++c) {
-    // the query this thread decides at the end of the chunk (slot c*256 + tid): its norm, fetched now
+    // the query this thread decides at the end of the chunk (slot c*256 + tid); its norm was requested a chunk ahead
     const int myslot = c * kChunkCols4 + tid;
     const int myf = myslot < nslots ? (GATHER ? (int)qsel[myslot] : myslot) : -1;
-    const int myna = (myf >= 0 && myf < nQ) ? normQ[myf] : OSFM_PAD_NORM;
-    // chunk c was requested during the first step of chunk c - 1 (chunk 0: above); everything this thread has in flight is older
+    const int myna = myna_next;  // fetched during the previous chunk's merge (chunk 0: with the prologue's loads)
+    // chunk c was requested at the top of the sweep of chunk c - 1 (chunk 0: above); everything this thread has in flight is older
     // than what the coming step will issue
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     __syncthreads();
     bb = sh.bbuf + (c & 1) * kChunkBytes4;
+    const int t0 = kCT4 - min(kCT4, tS - c * kCT4);  // the chunk has 8 - t0 query tiles: its steps enter the tile sequence at stage t0
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) bf[ks] = *(const v4i *)(bb + ks * 1024 + lane * 16);
 #pragma unroll
@@ -450,19 +494,18 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
     auto one_step = [&](const v4i (&cur)[kRT][4], v4i (&nxt)[kRT][4], int rb) {
       const int rbn = (rb + 1 < nrb) ? rb + 1 : 0;  // the next chunk starts over at row block 0 (the very last prefetch is unused)
       const bool live = rb * (kWaves * kRT) + w * kRT < tT;
-      const bool dma = (rb == 0) && (c + 1 < nchunks);
       const int nslot = (sidx + 1) & 1;
-      load_targets(rbn, nxt, nslot);
-      if (dma) dma_chunk(c + 1);  // its buffer was released by the merge of chunk c - 1
-      if (live) {
-        step(cur, rb, nslot, dma);
-      } else {  // a wave without targets in this row block still has to pick up the next step's seeds
+      if (live) {  // (a live step fetches the next step's targets itself: a full one in the gaps of its first tile)
+        step(cur, nxt, rb, rbn, nslot, t0, bb - t0 * OSFM_TILE_BYTES);
+      } else {  // a wave without targets in this row block still has to fetch the next step's, and pick up their seeds
+        load_targets(rbn, nxt, nslot);
         __builtin_amdgcn_s_waitcnt(0x0F70);
         read_seeds(nslot);
       }
       ++sidx;
     };
     OSFM_TICK(tk0)
+    if (c + 1 < nchunks) dma_chunk(c + 1);  // its buffer was released by the merge of chunk c - 1; older than every load of the sweep
     int rb = 0;
     for (; rb + 1 < nrb; rb += 2) {
       one_step(afA, afB, rb);
@@ -478,6 +521,7 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
 
     // ---- end of the chunk: merge the 8 partial classes (4 waves x 2 halves) of every query, decide, re-examine ----
     OSFM_TICK(tk1)
+    if (c + 1 < nchunks) myna_next = load_norm(c + 1);  // in flight during the merge; the next chunk's vmcnt(0) covers it
     __syncthreads();  // everyone is done reading the chunk: its buffer becomes the scratch
     OSFM_TICK(tk2)
     int *scr = (int *)(sh.bbuf + (c & 1) * kChunkBytes4);  // [8 parts][3][256]
@@ -485,9 +529,10 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       const int part = w * 2 + (lane >> 5);
 #pragma unroll
       for (int t = 0; t < kCT4; ++t) {
-        scr[(part * 3 + 0) * kChunkCols4 + t * 32 + (lane & 31)] = cb[t];
-        scr[(part * 3 + 1) * kChunkCols4 + t * 32 + (lane & 31)] = cs[t];
-        scr[(part * 3 + 2) * kChunkCols4 + t * 32 + (lane & 31)] = ci[t];
+        const int qt = (t - t0) & (kCT4 - 1);  // stage t held query tile t - t0 (the stages before t0 did not run: tiles that do not exist)
+        scr[(part * 3 + 0) * kChunkCols4 + qt * 32 + (lane & 31)] = cb[t];
+        scr[(part * 3 + 1) * kChunkCols4 + qt * 32 + (lane & 31)] = cs[t];
+        scr[(part * 3 + 2) * kChunkCols4 + qt * 32 + (lane & 31)] = ci[t];
       }
     }
     __syncthreads();
@@ -594,6 +639,7 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
           }
         }
         if (sl == 0 && !full) out[qf] = (unsigned short)win;
+        hit |= (!full && win != kNone);
         redo |= (full && sl == 0) ? (1ull << src) : 0ull;
       }
     }
@@ -647,6 +693,7 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       const float sec = wave_minf(bi0 == jwin ? bd1 : bd0);
       const bool ok = ratio < 0.0 ? (m < (float)(-ratio) * sec) : ((double)m < ratio * (double)sec);
       if (lane == 0) out[qf] = (unsigned short)(ok ? jwin : kNone);
+      hit |= ok;
     }
     while (!FQ && redo) {
       const int src = __builtin_ctzll(redo);
@@ -664,10 +711,14 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       const int m1 = wave_max(lv);
       const int jwin = -wave_max(lv == m1 ? -lj : INT_MIN);
       const int m2 = wave_max(lj == jwin ? ls : lv);
-      if (lane == 0) out[qf] = (unsigned short)(ratio_ok(qna - m1, qna - m2, ratio) ? jwin : kNone);
+      const bool ok = ratio_ok(qna - m1, qna - m2, ratio);
+      if (lane == 0) out[qf] = (unsigned short)(ok ? jwin : kNone);
+      hit |= ok;
     }
   }  // chunks
+  if (hit) *hit_word = 1;  // (every writer stores the same value)
   __syncthreads();
+  any_hit = *hit_word;
   return flag;
 }
 
@@ -713,7 +764,8 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   }
   if (tid == 0) {
     misc[8] = 0;
-    misc[9] = 0;
+    misc[9] = 0;   // hit word of pass A
+    misc[10] = 0;  // hit word of pass B
   }
   __syncthreads();
   // FQ: the float rows of the two images and the quantisation error bound of the pair
@@ -721,11 +773,14 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   const float *descA = FQ ? a.descf + a.tile_off[imgA] * (long)(32 * OSFM_DESC_DIM) : nullptr;
   const float *descB = FQ ? a.descf + a.tile_off[imgB] * (long)(32 * OSFM_DESC_DIM) : nullptr;
   const double eps = FQ ? (double)a.qerr[imgA] + (double)a.qerr[imgB] : 0.0;
+  // any: some query of the last pass run got a partner.  Without one the pair is empty (98 % of an exhaustive list): candidate
+  // list, pass B and the emission scan are skipped; the count and the flag (which may still ask for the exact re-run) are written
+  int any = 0;
   int flag = query_pass<false, FQ>(sh, tilesA, normA, nA, nA, nullptr, tilesB, normB, hnegB, nB, tiles_pad, hneg_pad, resA, a.ratio, tid,
-                                   descA, descB, eps);
+                                   descA, descB, eps, misc + 9, any);
   OSFM_TICK(tq1)
   OSFM_PHASE(10, tq0, tq1)  // pass A
-  if (a.symmetric) {
+  if (a.symmetric && any) {
     // candidates: the features of B that some row of A chose.  resB doubles as the mark array
     // (0 = chosen) until the candidate list is built, in ascending feature order.
     for (int q = tid; q < nA; q += kThreads) {
@@ -757,9 +812,9 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
     const int nK = base;
     OSFM_TICK(tq2)
     OSFM_PHASE(11, tq1, tq2)  // candidate list
-    if (nK > 0)
-      flag += query_pass<true, FQ>(sh, tilesB, normB, nB, nK, cand, tilesA, normA, hnegA, nA, tiles_pad, hneg_pad, resB, a.ratio, tid, descB, descA,
-                                   eps);
+    // (nK > 0: some resA named a feature of B)
+    flag += query_pass<true, FQ>(sh, tilesB, normB, nB, nK, cand, tilesA, normA, hnegA, nA, tiles_pad, hneg_pad, resB, a.ratio, tid, descB, descA,
+                                 eps, misc + 10, any);
   }
   OSFM_TICK(tq3)
   OSFM_PHASE(12, tq1, tq3)  // candidate list + pass B
@@ -773,7 +828,9 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   if (tid == 0) a.out_flags[p] = misc[8];
   // ---- ordered emission: over the features of the pair's first image, or (query_second) of its second image,
   //      the order in which the reference lists the matches of match_flann (matching.py:697) ----
-  {
+  if (!any) {
+    if (tid == 0) a.out_counts[p] = 0;
+  } else {
     const bool qs = !a.symmetric && a.query_second;
     const unsigned short *res1 = a.symmetric ? resB : resA;  // indexed by the emission feature -> its partner
     const unsigned short *res2 = a.symmetric ? resA : nullptr;
