@@ -598,6 +598,47 @@ int osfm_hahog_extract_batch(osfm_ctx *ctx, int n_images, const float *const *im
                              float edge_threshold, int target_num_features, int flags, float *const *points, float *const *desc,
                              const int *capacities, int *n_features, int concurrency);
 
+/* =====================================================================================
+ * Culling of the final point cloud (opensfm/reconstruction.py:1590-1594 -> sfm/src/map_helpers.cc), cloud.hip
+ *
+ * osfm_points_conditioning  restates FilterBadlyConditionedPoints (map_helpers.cc:20-164) with ComputePointInverseCovariance
+ *   (geometry/src/covariance.cc):
+ *   points      n_points x 3;  shot_pose  n_shots x 12: R (row-major) then t of the WORLD-TO-CAMERA pose of every shot, already composed
+ *               with its rig;  shot_camera  n_shots indices into the camera table cam_model (n_cams) / cam_params (n_cams x 16, the
+ *               layout listed at the OSFM_CAMERA_* definitions; all ten models);  obs_shot / obs_point  n_obs, in any order.
+ *   Per landmark, over its observations in ascending input order: kept only if some pair of rays normalize(X - origin) has
+ *   AngleBetweenVectors (triangulation.cc:66-73) > min_angle_deg * pi / 180 (strict; a NaN angle, 0 or 1 observations do not keep it);
+ *   H = sum J^T J with J the 2 x 3 derivative of the projection with respect to the world point; rejected when H is not finite, when
+ *   det H is not finite or |det H| < min_abs_det, when the smallest eigenvalue of H is <= 0 or not finite; otherwise
+ *   cond = min(sqrt(lambda_max / lambda_min), 1000) (the eigenvalues of H itself, cyclic Jacobi: the ratio the reference takes from
+ *   H^-1).  Then, sequentially in landmark order on the host: threshold = mean + 1.0 * population sigma of the surviving cond values,
+ *   and every landmark with cond > threshold is removed.
+ *   cond     n_points: NaN where rejected before the threshold;
+ *   reason   n_points: 0 kept, 1 ray angle, 2 H not finite, 3 determinant, 4 eigenvalues, 5 above the threshold;
+ *   threshold  NaN when no landmark reached the statistics;  n_removed  landmarks with reason != 0.
+ *   min_angle_deg must lie in [0, 180].  No floating-point atomics: two runs are bit-equal.
+ *
+ * osfm_points_isolation  restates RemoveIsolatedPoints (map_helpers.cc:166-231): the positions cast to float32; per point the k + 1
+ *   smallest squared L2 distances to all points (itself included) in float32 as ((dx*dx) + dy*dy) + dz*dz without contraction, the
+ *   smallest dropped, the other k summed in ascending order in float64 and divided by k; threshold = mean + 1.25 * population sigma
+ *   of these averages (sequentially in input order); removed[i] = avg[i] > threshold.  The search is exact (uniform grid, rings of
+ *   cells, brute force for the queries the rings do not settle).  The grid does not span the bounding box but the 2 % .. 98 % quantile
+ *   box of every axis (six selections over n floats on the host before the kernels); points outside it are clamped into the border
+ *   cells, which keeps the result exact and keeps a few far points from stretching the cells.  Limits: a cloud with more than 2 % of
+ *   its points far out on one side of an axis stretches the cells along it anyway, and a cloud whose bulk sits in a few cells of that
+ *   box degrades towards all-pairs inside them -- both exact, both slow at scale.  n_points <= k removes nothing, as the reference does (avg and
+ *   threshold NaN: nothing was computed).  1 <= k <= 31, and every coordinate must be finite as a float32 -- the reference's
+ *   behaviour on non-finite coordinates is undefined: OSFM_E_INVALID otherwise.
+ *
+ * kernel_ms (both, may be NULL): device time of the kernels.  n_points == 0 / n_obs == 0 return without a launch.
+ * ===================================================================================== */
+int osfm_points_conditioning(osfm_ctx *ctx, const double *points, int n_points, const double *shot_pose, const int32_t *shot_camera, int n_shots,
+                             const int32_t *cam_model, const double *cam_params, int n_cams, const int32_t *obs_shot, const int32_t *obs_point,
+                             int64_t n_obs, double min_angle_deg, double min_abs_det, double *cond, uint8_t *reason, double *threshold,
+                             int *n_removed, double *kernel_ms);
+int osfm_points_isolation(osfm_ctx *ctx, const double *points, int n_points, int k, double *avg, uint8_t *removed, double *threshold,
+                          int *n_removed, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,17 @@ SIGNATURES = {
         [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
          C.POINTER(C.c_double), C.c_int, C.POINTER(RelrotParams), C.POINTER(RelrotResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
     ),
+    "osfm_points_conditioning": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+         C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_uint8),
+         C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)],
+    ),
+    "osfm_points_isolation": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(C.c_int),
+         C.POINTER(C.c_double)],
+    ),
     "osfm_match_guided": (
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float),

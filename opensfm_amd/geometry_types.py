@@ -324,6 +324,13 @@ class Landmark:
         self.id = landmark_id
         self.coordinates = np.asarray(coordinates, float).copy()
         self.reprojection_errors: Dict[str, np.ndarray] = {}
+        self._map: Optional["Reconstruction"] = None  # set by Reconstruction.create_point: the observations live on the shots
+
+    def number_of_observations(self) -> int:
+        """``Landmark::NumberOfObservations``: the shots of the landmark's map that observe it"""
+        if self._map is None:
+            raise RuntimeError(f"landmark {self.id!r} belongs to no map: create it with Reconstruction.create_point")
+        return len(self._map._observers.get(self.id, ()))
 
 
 class GroundControlPointObservation:
@@ -373,6 +380,7 @@ class Reconstruction:
         self.points: Dict[str, Landmark] = {}
         self.biases: Dict[str, Similarity] = {}
         self.reference = TopocentricConverter()
+        self._observers: Dict[str, set] = {}  # landmark id -> ids of the shots that observe it, kept by add_ / remove_observation
 
     @property
     def map(self) -> "Reconstruction":
@@ -405,10 +413,28 @@ class Reconstruction:
 
     def create_point(self, point_id: str, coordinates) -> Landmark:
         self.points[point_id] = Landmark(point_id, coordinates)
+        self.points[point_id]._map = self
         return self.points[point_id]
 
     def add_observation(self, shot_id: str, point_id: str, observation: Observation) -> None:
         self.shots[shot_id].observations[point_id] = observation
+        self._observers.setdefault(point_id, set()).add(shot_id)
+
+    def get_landmarks(self) -> Dict[str, Landmark]:
+        """``Map::GetLandmarks``"""
+        return self.points
+
+    def remove_observation(self, shot_id: str, lm_id: str) -> None:
+        """``Map::RemoveObservation`` (map.cc): the shot no longer observes the landmark; the landmark itself stays"""
+        del self.shots[shot_id].observations[lm_id]
+        self._observers[lm_id].discard(shot_id)
+
+    def remove_landmark(self, lm) -> None:
+        """``Map::RemoveLandmark``: a ``Landmark`` or its id; its observations leave the shots that hold them"""
+        lm_id = lm if isinstance(lm, str) else lm.id
+        del self.points[lm_id]
+        for shot_id in self._observers.pop(lm_id, ()):
+            del self.shots[shot_id].observations[lm_id]
 
 
 def optional_value(x) -> Optional[Any]:

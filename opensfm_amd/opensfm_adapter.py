@@ -502,3 +502,136 @@ def bundle_shot_poses(reconstruction, shot_ids, camera_priors: Dict[str, Any], r
     timer_teardown = time.perf_counter()
     return {"brief_report": ba.brief_report(),
             "wall_times": {"setup": timer_setup - start, "run": timer_run - timer_setup, "teardown": timer_teardown - timer_run}}
+
+
+# ------------------------------------------------------------------------------------------------
+# culling of the final point cloud (reconstruction.py:1590-1594 calls these through pysfm)
+# ------------------------------------------------------------------------------------------------
+def _map_landmarks(map_) -> Dict[str, Any]:
+    return map_.points if hasattr(map_, "points") else map_.get_landmarks()
+
+
+def _map_shots(map_) -> Dict[str, Any]:
+    return map_.shots if hasattr(map_, "shots") else map_.get_shots()
+
+
+def _remove_flagged(map_, lm_ids: List[str], flags) -> int:
+    landmarks = _map_landmarks(map_)
+    removed = 0
+    for lm_id, flag in zip(lm_ids, flags):
+        if flag and lm_id in landmarks:
+            map_.remove_landmark(landmarks[lm_id])
+            removed += 1
+    return removed
+
+
+def flatten_cloud(map_) -> Dict[str, Any]:
+    """The arrays ``osfm_points_conditioning`` takes, from the map the way ``bundle`` walks it: landmarks in map order, the cameras the
+    shots use through ``matching.camera_parameters``, every shot's world-to-camera pose composed with its rig (``shot.pose``), the
+    observations shot by shot.  Observations of landmarks the map does not hold are skipped."""
+    from .matching import camera_parameters
+
+    landmarks = _map_landmarks(map_)
+    lm_ids = list(landmarks.keys())
+    lm_index = {lm_id: i for i, lm_id in enumerate(lm_ids)}
+    points = np.array([np.asarray(landmarks[i].coordinates, float) for i in lm_ids], np.float64).reshape(-1, 3)
+    cam_index: Dict[str, int] = {}
+    models, params = [], []
+    shots = _map_shots(map_)
+    shot_pose = np.zeros((len(shots), 12))
+    shot_camera = np.zeros(len(shots), np.int32)
+    obs_shot, obs_point = [], []
+    for s, shot in enumerate(shots.values()):
+        cam = shot.camera
+        if cam.id not in cam_index:
+            model, par = camera_parameters(cam)
+            cam_index[cam.id] = len(models)
+            models.append(model)
+            params.append(par)
+        shot_camera[s] = cam_index[cam.id]
+        pose = shot.pose
+        shot_pose[s, :9] = np.asarray(pose.get_R_world_to_cam(), float).reshape(9)
+        shot_pose[s, 9:] = np.asarray(pose.get_t_world_to_cam(), float).reshape(3)
+        for lm_id, _ in _shot_observations(shot):
+            p = lm_index.get(lm_id)
+            if p is not None:
+                obs_shot.append(s)
+                obs_point.append(p)
+    return {"lm_ids": lm_ids, "points": points, "shot_pose": shot_pose, "shot_camera": shot_camera,
+            "cam_model": np.array(models, np.int32), "cam_params": np.array(params, np.float64).reshape(-1, 16),
+            "obs_shot": np.array(obs_shot, np.int32), "obs_point": np.array(obs_point, np.int32)}
+
+
+def points_conditioning(points, shot_pose, shot_camera, cam_model, cam_params, obs_shot, obs_point, min_angle_deg: float = 1.0,
+                        min_abs_det: float = 1e-15, ctx=None) -> Dict[str, Any]:
+    """``osfm_points_conditioning`` on arrays -> cond (NaN where rejected earlier), reason (0 keep, 1 angle, 2 non-finite, 3 determinant,
+    4 eigenvalues, 5 above the threshold), threshold, removed, kernel_ms"""
+    import ctypes as C
+
+    from ._lib import check, default_context, load
+
+    ctx = ctx or default_context()
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    shot_pose = np.ascontiguousarray(shot_pose, np.float64).reshape(-1, 12)
+    shot_camera = np.ascontiguousarray(shot_camera, np.int32)
+    cam_model = np.ascontiguousarray(cam_model, np.int32)
+    cam_params = np.ascontiguousarray(cam_params, np.float64).reshape(-1, 16)
+    obs_shot = np.ascontiguousarray(obs_shot, np.int32)
+    obs_point = np.ascontiguousarray(obs_point, np.int32)
+    if len(shot_camera) != len(shot_pose) or len(cam_params) != len(cam_model) or len(obs_shot) != len(obs_point):
+        raise ValueError("points_conditioning: array lengths do not agree")
+    n = len(points)
+    cond, reason = np.full(max(n, 1), np.nan), np.zeros(max(n, 1), np.uint8)
+    thr, removed, ms = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
+
+    def ptr(a, t):
+        return a.ctypes.data_as(C.POINTER(t))
+
+    check(load().osfm_points_conditioning(ctx.handle, ptr(points, C.c_double), n, ptr(shot_pose, C.c_double), ptr(shot_camera, C.c_int32),
+                                          len(shot_pose), ptr(cam_model, C.c_int32), ptr(cam_params, C.c_double), len(cam_model),
+                                          ptr(obs_shot, C.c_int32), ptr(obs_point, C.c_int32), len(obs_shot), float(min_angle_deg),
+                                          float(min_abs_det), ptr(cond, C.c_double), ptr(reason, C.c_uint8), C.byref(thr), C.byref(removed),
+                                          C.byref(ms)), "osfm_points_conditioning")
+    return {"cond": cond[:n], "reason": reason[:n], "threshold": thr.value, "removed": removed.value, "kernel_ms": ms.value}
+
+
+def points_isolation(points, k: int = 7, ctx=None) -> Dict[str, Any]:
+    """``osfm_points_isolation`` on an (n, 3) array -> avg (mean squared distance to the k nearest neighbours, float32 arithmetic as the
+    reference's kd-tree), removed (bool), threshold, count, kernel_ms.  Raises for k outside 1 .. 31 and for non-finite coordinates."""
+    import ctypes as C
+
+    from ._lib import check, default_context, load
+
+    ctx = ctx or default_context()
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = len(points)
+    avg, flags = np.full(max(n, 1), np.nan), np.zeros(max(n, 1), np.uint8)
+    thr, removed, ms = C.c_double(0.0), C.c_int(0), C.c_double(0.0)
+    check(load().osfm_points_isolation(ctx.handle, points.ctypes.data_as(C.POINTER(C.c_double)), n, int(k), avg.ctypes.data_as(C.POINTER(C.c_double)),
+                                       flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(thr), C.byref(removed), C.byref(ms)),
+          "osfm_points_isolation")
+    return {"avg": avg[:n], "removed": flags[:n].astype(bool), "threshold": thr.value, "count": removed.value, "kernel_ms": ms.value}
+
+
+def filter_badly_conditioned_points(map, min_angle_deg: float = 1.0, min_abs_det: float = 1e-15) -> int:  # noqa: A002 (the reference's name)
+    """``pysfm.filter_badly_conditioned_points`` (sfm/python/pybind.cc:22-25 -> map_helpers.cc:20-164): removes the landmarks without a pair
+    of rays wider than ``min_angle_deg``, with a degenerate inverse covariance, or with a condition number above mean + sigma; returns
+    how many were removed"""
+    flat = flatten_cloud(map)
+    if not flat["lm_ids"]:
+        return 0
+    res = points_conditioning(flat["points"], flat["shot_pose"], flat["shot_camera"], flat["cam_model"], flat["cam_params"], flat["obs_shot"],
+                              flat["obs_point"], min_angle_deg, min_abs_det)
+    return _remove_flagged(map, flat["lm_ids"], res["reason"] != 0)
+
+
+def remove_isolated_points(map, k: int = 7) -> int:  # noqa: A002
+    """``pysfm.remove_isolated_points`` (pybind.cc:27-29 -> map_helpers.cc:166-231): removes the landmarks whose mean squared distance to
+    their ``k`` nearest neighbours exceeds mean + 1.25 sigma; returns how many were removed"""
+    landmarks = _map_landmarks(map)
+    lm_ids = list(landmarks.keys())
+    if not lm_ids:
+        return 0
+    points = np.array([np.asarray(landmarks[i].coordinates, float) for i in lm_ids], np.float64).reshape(-1, 3)
+    res = points_isolation(points, k)
+    return _remove_flagged(map, lm_ids, res["removed"])

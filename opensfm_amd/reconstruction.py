@@ -4,7 +4,11 @@
 ``compute_image_pairs(track_dict, data)`` takes what ``tracking.all_common_tracks_with_features`` returns, concatenates the pairs'
 normalised image coordinates in item order, computes the bearings and runs ``pyrobust.ransac_relative_rotation`` for every pair in
 one call, counts the rotation-only inliers and the reconstructability on the device, and sorts on the host exactly as the reference
-does (``np.argsort(-np.array(score))``)."""
+does (``np.argsort(-np.array(score))``).
+
+``cull_final_point_cloud(reconstruction, config)`` is the tail of ``grow_reconstruction`` after its last bundle
+(``reconstruction.py:1586-1594``): the outlier step (``discard_gross_observations``) and, under ``filter_final_point_cloud``, the two point-cloud filters on the GPU
+(``cloud.hip``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -133,3 +137,59 @@ def compute_image_pairs(track_dict: Dict[Tuple[str, str], Any], data, ctx=None) 
     score = [int(r["reconstructability"]) for r in res if r["reconstructability"] > 0]
     order = np.argsort(-np.array(score))
     return [pairs[o] for o in order]
+
+
+def _residual_table(landmarks) -> Tuple[List[Tuple[str, str]], np.ndarray]:
+    """every reprojection error the last bundle stored on the landmarks: its (landmark id, shot id) and the errors as rows of one array"""
+    keys = [(lm_id, shot_id) for lm_id, lm in landmarks.items() for shot_id in lm.reprojection_errors]
+    rows = np.array([landmarks[lm_id].reprojection_errors[shot_id] for lm_id, shot_id in keys], np.float64)
+    return keys, rows.reshape(len(keys), -1) if keys else np.zeros((0, 2))
+
+
+def _residual_limit(config: Dict[str, Any], rows: np.ndarray) -> float:
+    """the largest reprojection error an observation may keep.  ``bundle_outlier_filtering_type`` FIXED: the configured constant.  AUTO: a
+    robust scale of all residuals -- the componentwise median m, 1.486 times the median distance to it as the spread s, and
+    ``bundle_outlier_auto_ratio`` * |m + s|.  Anything else: 1.  A missing key is a KeyError, as in the reference."""
+    mode = config["bundle_outlier_filtering_type"]
+    if mode == "FIXED":
+        return float(config["bundle_outlier_fixed_threshold"])
+    if mode == "AUTO":
+        centre = np.median(rows, axis=0)
+        spread = 1.486 * np.median(np.sqrt(((rows - centre) ** 2).sum(axis=1)))
+        return float(config["bundle_outlier_auto_ratio"]) * float(np.linalg.norm(centre + spread))
+    return 1.0
+
+
+def discard_gross_observations(reconstruction, config: Dict[str, Any]) -> int:
+    """The outlier step after a bundle, with the result of the reference's ``remove_outliers`` (which itself runs unmodified on
+    ``geometry_types.Reconstruction``; this one is for callers that do not load the reference's module).  One vectorised pass over the
+    table of stored reprojection errors: an observation whose first two error components exceed the limit in norm leaves its shot, and a
+    landmark that lost one and has fewer than two left leaves the map.  Returns the number of observations discarded."""
+    landmarks = reconstruction.points
+    keys, rows = _residual_table(landmarks)
+    if not keys:
+        return 0
+    limit = _residual_limit(config, rows)
+    gross = np.flatnonzero(rows[:, 0] ** 2 + rows[:, 1] ** 2 > limit * limit)
+    thinned = dict.fromkeys(keys[i][0] for i in gross)  # in first-hit order, each once
+    for i in gross:
+        lm_id, shot_id = keys[i]
+        reconstruction.map.remove_observation(shot_id, lm_id)
+    for lm_id in thinned:
+        if landmarks[lm_id].number_of_observations() < 2:
+            reconstruction.map.remove_landmark(landmarks[lm_id])
+    return len(gross)
+
+
+def cull_final_point_cloud(reconstruction, config: Dict[str, Any]) -> Dict[str, int]:
+    """What ``grow_reconstruction`` does after its final bundle, for callers that do not load the reference's module: the outlier step and,
+    if ``config["filter_final_point_cloud"]``, ``pysfm.filter_badly_conditioned_points`` with ``config["triangulation_min_ray_angle"]``
+    and ``pysfm.remove_isolated_points``.  The keys are read as the reference reads them: a missing one is a KeyError.  Returns what each
+    step removed."""
+    from . import opensfm_adapter
+
+    report = {"outlier_observations": discard_gross_observations(reconstruction, config), "badly_conditioned": 0, "isolated": 0}
+    if config["filter_final_point_cloud"]:
+        report["badly_conditioned"] = opensfm_adapter.filter_badly_conditioned_points(reconstruction.map, config["triangulation_min_ray_angle"])
+        report["isolated"] = opensfm_adapter.remove_isolated_points(reconstruction.map)
+    return report
