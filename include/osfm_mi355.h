@@ -639,6 +639,49 @@ int osfm_points_conditioning(osfm_ctx *ctx, const double *points, int n_points, 
 int osfm_points_isolation(osfm_ctx *ctx, const double *points, int n_points, int k, double *avg, uint8_t *removed, double *threshold,
                           int *n_removed, double *kernel_ms);
 
+/* =====================================================================================
+ * Triangulation of tracks (opensfm/reconstruction.py:1032-1073 TrackTriangulator.triangulate, `triangulation_type: FULL`), triangulate.hip
+ *
+ * Per track, over its observations in input order: fewer than 2 -> status 1.  TriangulateBearingsMidpoint (geometry/src/triangulation.cc:
+ * 139-178): some pair (i, j < i) must have AngleBetweenVectors (through acos; 0 when |cos| >= 1) in [min_angle, pi - min_angle], else
+ * status 2; the midpoint X = (I + BBt Cinv) A / n - Cinv BBtA; per observation in order, AngleBetweenVectors(X - o_i, w_i) > threshold
+ * -> status 3, then (X - o_i) . w_i < min_depth -> status 4 (these very comparisons: a NaN angle passes).  A valid midpoint goes through
+ * PointRefinement (triangulation.cc:221-233: Ceres' TinySolver, max_num_iterations = refinement_iterations, restated in
+ * triangulate_core.h) and its result is stored without a further test -- with ONE divergence: a midpoint or a refined point that is
+ * not finite is status 5, where the reference would store the NaN point (with finite input that takes min_angle_deg = 0 and parallel
+ * rays).
+ *   status           n_tracks: 0 triangulated, 1 fewer than 2 observations, 2 ray angle, 3 reprojection angle, 4 depth, 5 not finite;
+ *   points           n_tracks x 3: NaN unless the status is 0;
+ *   iterations_used  n_tracks: TinySolver's summary.iterations (0 unless the status is 0 or 5);  kernel_ms may be NULL.
+ * Track t owns rows track_offsets[t] : track_offsets[t + 1] (n_tracks + 1 offsets, the first 0, non-decreasing).
+ * osfm_triangulate_bearings  centers / bearings: the origins and bearings of the rows, already in world coordinates.
+ * osfm_triangulate_tracks    obs_shot / obs_xy (normalised image coordinates) per row; shot_pose, shot_camera, cam_model, cam_params as
+ *   for osfm_points_conditioning.  The kernel computes b = pixel_bearing, w = R^T b and o = -R^T t as it loads a row.
+ * OSFM_E_INVALID: offsets that decrease or do not start at 0, a shot or camera index out of range, a non-finite observation or a
+ * non-finite pose used by one (found by the kernel as it loads the rows), refinement_iterations < 0, min_angle_deg outside [0, 180].
+ * n_tracks == 0 returns without a launch.  Every sum runs in an order fixed by the track's length alone, without floating-point
+ * atomics: two runs are bit-equal.
+ * ===================================================================================== */
+typedef struct osfm_triangulate_params {
+  double threshold;              /* triangulation_threshold: radians */
+  double min_angle_deg;          /* triangulation_min_ray_angle */
+  double min_depth;              /* triangulation_min_depth */
+  int32_t refinement_iterations; /* triangulation_refinement_iterations */
+  int32_t pad;
+} osfm_triangulate_params;
+/* the values of opensfm/config.py: 0.006, 1.0, 0.001, 10 */
+void osfm_triangulate_params_default(osfm_triangulate_params *p);
+int osfm_triangulate_bearings(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                              const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used, double *kernel_ms);
+/* PointRefinement alone (pygeometry.point_refinement for a batch): every track's `initial` point (n_tracks x 3) goes through the solver
+ * over the track's rows and the result is stored as it is, without any test -- also for tracks of 0 or 1 rows. */
+int osfm_triangulate_refine(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                            const double *initial, int refinement_iterations, double *points, int32_t *iterations_used, double *kernel_ms);
+int osfm_triangulate_tracks(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
+                            const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy, const int64_t *track_offsets,
+                            int n_tracks, const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used,
+                            double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,16 @@ class RelrotResult(C.Structure):
     ]
 
 
+class TriangulateParams(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("min_angle_deg", C.c_double),
+        ("min_depth", C.c_double),
+        ("refinement_iterations", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class RelposeResult(C.Structure):
     _fields_ = [
         ("model", C.c_double * 12),
@@ -176,6 +186,23 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(C.c_int),
          C.POINTER(C.c_double)],
+    ),
+    "osfm_triangulate_params_default": (None, [C.POINTER(TriangulateParams)]),
+    "osfm_triangulate_bearings": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams),
+         C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    ),
+    "osfm_triangulate_refine": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_double), C.c_int,
+         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    ),
+    "osfm_triangulate_tracks": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int,
+         C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams), C.POINTER(C.c_double),
+         C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
     ),
     "osfm_match_guided": (
         C.c_int,

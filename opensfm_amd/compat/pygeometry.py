@@ -1,0 +1,55 @@
+"""Two leaves of the reference's ``pygeometry`` (``opensfm/src/geometry/python/pybind.cc:298,309``) under its argument names, served by
+``triangulate.hip``: ``triangulate_bearings_midpoint`` and ``point_refinement``.  One call is one track on the GPU -- these exist so that
+code written against the leaves (``TrackTriangulator``) runs unchanged; the batched path is
+``opensfm_amd.reconstruction.triangulate_shot_features`` / ``retriangulate``.
+
+This module is NOT registered by ``compat.install()`` (``compat.MODULES`` stays as it is): import it directly,
+``from opensfm_amd.compat import pygeometry``."""
+from typing import Sequence, Tuple
+
+import numpy as np
+
+from .. import reconstruction as _reconstruction
+from .._lib import check as _check, default_context as _default_context, load as _load
+
+
+def triangulate_bearings_midpoint(centers, bearings, threshold_list: Sequence[float], min_angle: float, min_depth: float) -> Tuple[bool, np.ndarray]:
+    """``geometry::TriangulateBearingsMidpoint`` (triangulation.cc:139-178): (valid, X).  ``min_angle`` in radians.  A threshold list
+    shorter than the rows returns (False, ...) as the reference does; the device call takes ONE threshold, so thresholds that are not all
+    equal raise NotImplementedError.  X is NaN when the triangulation is not valid (the reference returns an uninitialised vector), and a
+    midpoint that is not finite is not valid (the one divergence of ``osfm_triangulate_bearings``)."""
+    centers = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+    bearings = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    thresholds = np.asarray(threshold_list, np.float64).reshape(-1)
+    if len(thresholds) < len(centers):
+        return False, np.full(3, np.nan)
+    thresholds = thresholds[: len(centers)]
+    if len(thresholds) and not (thresholds == thresholds[0]).all():
+        raise NotImplementedError("triangulate_bearings_midpoint: one threshold per call on the GPU path; the list holds different values")
+    if len(centers) < 2:  # (the pair loop of the reference finds no pair)
+        return False, np.full(3, np.nan)
+    # refinement_iterations = 0: the solver evaluates once and takes no step, so the point that comes back is the midpoint
+    points, status, _, _ = _reconstruction.triangulate_bearings_arrays(centers, bearings, [0, len(centers)], float(thresholds[0]),
+                                                                     float(np.degrees(min_angle)), float(min_depth), 0)
+    return bool(status[0] == 0), points[0].copy()
+
+
+def point_refinement(centers, bearings, point, iterations: int) -> np.ndarray:
+    """``geometry::PointRefinement`` (triangulation.cc:221-233): TinySolver with ``max_num_iterations = iterations`` from ``point``"""
+    import ctypes as C
+
+    centers = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+    bearings = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    if len(centers) != len(bearings):
+        raise ValueError("point_refinement: centers and bearings do not agree")
+    initial = np.ascontiguousarray(point, np.float64).reshape(3)
+    offsets = np.array([0, len(centers)], np.int64)
+    out, used, ms = np.full(3, np.nan), np.zeros(1, np.int32), C.c_double(0.0)
+
+    def ptr(a, t):
+        return a.ctypes.data_as(C.POINTER(t))
+
+    _check(_load().osfm_triangulate_refine(_default_context().handle, ptr(centers, C.c_double), ptr(bearings, C.c_double), ptr(offsets, C.c_int64), 1,
+                                           ptr(initial, C.c_double), int(iterations), ptr(out, C.c_double), ptr(used, C.c_int32), C.byref(ms)),
+           "osfm_triangulate_refine")
+    return out

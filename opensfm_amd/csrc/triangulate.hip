@@ -1,0 +1,367 @@
+// triangulate.hip -- triangulation of reconstruction tracks on gfx950: TrackTriangulator.triangulate (opensfm/reconstruction.py:1032-1073,
+// `triangulation_type: FULL`) for every track of a batch in one call -- what triangulate_shot_features and retriangulate do track by track.
+//
+// The numerics and the per-track walk live in triangulate_core.h (host + device); this file adds the lane policies, the kernels and the
+// C ABI.
+//   tri_group_kernel  a group of kGroup = 8 lanes per track (eight tracks per wavefront, the shape of cloud.hip) for the tracks of at
+//                     most kGroupObs observations;
+//   tri_wave_kernel   one wavefront per track for the longer ones (a compacted list the host builds while it checks the offsets).
+// A lane loads the observations i = lane, lane + G, ... of its track ONCE -- for osfm_triangulate_tracks that is where the bearing
+// b = pixel_bearing(xy), w = R^T b and o = -R^T t are computed and where the row is validated -- and parks (o, w) in LDS, where the pair
+// test, the midpoint sums, the two per-observation tests and every evaluation of the refinement read them.  Only a track longer than
+// the kWaveObs observations a wavefront's LDS slice holds loads the overhang again.
+// Sums: every lane adds its observations in ascending order, then a butterfly over the group (log2 G xor-shuffles): the order depends
+// on the track's length alone (which kernel, which lane), never on the grid or on timing; no atomics on floating-point values.
+#include <math.h>
+
+#include <vector>
+
+#include "osfm_internal.h"
+#include "triangulate_core.h"
+
+using namespace osfm_tri;
+
+namespace {
+
+constexpr int kGroup = 8;  // lanes per short track
+#ifndef OSFM_TRI_GROUP_OBS
+#define OSFM_TRI_GROUP_OBS 32  // the measured split: 8 is 7 x slower on 10-observation tracks, 16 ties, 64 loses occupancy to LDS
+#endif
+constexpr int kGroupObs = OSFM_TRI_GROUP_OBS;  // longest track of the group kernel
+constexpr int kGroupPitch = kGroupObs + 1;     // LDS doubles per group and component (odd: the groups of a wavefront start on different banks)
+constexpr int kBlock = 256;
+constexpr int kGroupsPerBlock = kBlock / kGroup;
+constexpr int kWave = 64;
+constexpr int kWaveObs = 512;  // observations of a long track kept in LDS (24 KiB)
+constexpr int kMaxTrack = 1 << 24;
+
+// rows that are world-space origins and bearings already
+struct BearingRows {
+  const double *centers, *bearings;
+  __device__ __forceinline__ bool load(int64_t row, double *o, double *w) const {
+    for (int k = 0; k < 3; k++) {
+      o[k] = centers[3 * row + k];
+      w[k] = bearings[3 * row + k];
+    }
+    return true;
+  }
+};
+
+// rows that are (shot, normalised image point): Camera::Bearing, then into the world with the shot's pose; false for a row that cannot
+// be evaluated (shot index outside the table, non-finite point or pose)
+struct PixelRows {
+  const double *shot_pose;
+  const int32_t *shot_camera, *cam_model;
+  const double *cam_params;
+  const int32_t *obs_shot;
+  const double *obs_xy;
+  int n_shots;
+  __device__ __forceinline__ bool load(int64_t row, double *o, double *w) const {
+    const int s = obs_shot[row];
+    const double x = obs_xy[2 * row], y = obs_xy[2 * row + 1];
+    bool ok = s >= 0 && s < n_shots && finite_d(x) && finite_d(y);
+    double P[12];
+    for (int k = 0; k < 12; k++) {
+      P[k] = ok ? shot_pose[12 * (size_t)s + k] : NAN;
+      ok = ok && finite_d(P[k]);
+    }
+    if (!ok) {
+      for (int k = 0; k < 3; k++) o[k] = w[k] = NAN;
+      return false;
+    }
+    const int c = shot_camera[s];
+    double b[3];
+    osfm_rp::pixel_bearing_generic(cam_model[c], cam_params + 16 * (size_t)c, x, y, b);
+    for (int k = 0; k < 3; k++) {
+      w[k] = (P[k] * b[0] + P[3 + k] * b[1]) + P[6 + k] * b[2];       // R^T b
+      o[k] = -((P[k] * P[9] + P[3 + k] * P[10]) + P[6 + k] * P[11]);  // Pose::GetOrigin: -R^T t
+    }
+    return true;
+  }
+};
+
+// G lanes on one track; (o, w) of observation i < cap at sh[c * plane + i], c = 0 .. 5.  Overhang: the track may be longer than cap
+template <int G, bool Overhang, class Rows>
+struct LaneTrack {
+  int n, lane, cap, plane;
+  const double *sh;
+  Rows rows;
+  int64_t row0;
+  __device__ __forceinline__ int first() const { return lane; }
+  __device__ __forceinline__ int stride() const { return G; }
+  __device__ __forceinline__ void at(int i, double *o, double *w) const {
+    if (!Overhang || i < cap) {
+      for (int k = 0; k < 3; k++) {
+        o[k] = sh[k * plane + i];
+        w[k] = sh[(3 + k) * plane + i];
+      }
+    } else {
+      again(row0 + i, o, w);
+    }
+  }
+  // the overhang of a track longer than the LDS slice (validated when the track was staged); out of line: one copy, not one per reader
+  __device__ __attribute__((noinline)) void again(int64_t row, double *o, double *w) const { (void)rows.load(row, o, w); }
+  template <class F>
+  __device__ __forceinline__ void each(F f) const {
+    for (int i = lane; i < n; i += G) {
+      double o[3], w[3];
+      at(i, o, w);
+      f(i, o, w);
+    }
+  }
+  __device__ __forceinline__ void sum(double *v, int m) const {
+    for (int mask = 1; mask < G; mask <<= 1)
+      for (int k = 0; k < m; k++) v[k] += __shfl_xor(v[k], mask, 64);
+  }
+  __device__ __forceinline__ int lowest(int key) const {
+    for (int mask = 1; mask < G; mask <<= 1) {
+      const int other = __shfl_xor(key, mask, 64);
+      key = other < key ? other : key;
+    }
+    return key;
+  }
+  __device__ __forceinline__ bool any(bool b) const {
+    int v = b ? 1 : 0;
+    for (int mask = 1; mask < G; mask <<= 1) v |= __shfl_xor(v, mask, 64);
+    return v != 0;
+  }
+};
+
+struct Out {
+  double *points;
+  uint8_t *status;
+  int32_t *iterations;
+  int *bad;  // set when a row could not be evaluated
+  const double *initial;  // osfm_triangulate_refine: n_tracks x 3 starting points -- PointRefinement alone, no test; else null
+};
+
+// lanes lane, lane + G, ... of a track's first `cap` observations into LDS
+template <int G, class Rows>
+__device__ __forceinline__ void stage(const Rows &rows, int64_t row0, int n, int cap, int lane, double *sh, int plane, int *bad) {
+  bool ok = true;
+  for (int i = lane; i < n; i += G) {
+    double o[3], w[3];
+    ok = rows.load(row0 + i, o, w) && ok;
+    if (i < cap)
+      for (int k = 0; k < 3; k++) {
+        sh[k * plane + i] = o[k];
+        sh[(3 + k) * plane + i] = w[k];
+      }
+  }
+  if (!ok) atomicOr(bad, 1);
+}
+
+template <class Track>
+__device__ __forceinline__ void solve_and_store(Track &trk, const Params &prm, int64_t t, const Out &out) {
+  double X[3] = {NAN, NAN, NAN};
+  int iterations = 0;
+  int status = kOk;
+  if (out.initial) {
+    for (int k = 0; k < 3; k++) X[k] = out.initial[3 * t + k];
+    iterations = refine(trk, prm.iterations, X);
+  } else {
+    status = triangulate_track(trk, prm, X, &iterations);
+  }
+  if (trk.lane != 0) return;
+  for (int k = 0; k < 3; k++) out.points[3 * t + k] = X[k];
+  out.status[t] = (uint8_t)status;
+  out.iterations[t] = iterations;
+}
+
+template <class Rows>
+__global__ __launch_bounds__(kBlock) void tri_group_kernel(Rows rows, const int64_t *__restrict__ offsets, int n_tracks, Params prm, Out out) {
+  __shared__ double sh[6 * kGroupsPerBlock * kGroupPitch];
+  const int g = (int)threadIdx.x / kGroup, lane = (int)threadIdx.x % kGroup;
+  const int64_t t = (int64_t)blockIdx.x * kGroupsPerBlock + g;
+  const int64_t row0 = t < n_tracks ? offsets[t] : 0;
+  const int64_t len = t < n_tracks ? offsets[t + 1] - row0 : 0;
+  const bool mine = t < n_tracks && len <= kGroupObs;  // the same on every lane of the group
+  const int n = mine ? (int)len : 0;
+  constexpr int plane = kGroupsPerBlock * kGroupPitch;
+  double *slice = sh + g * kGroupPitch;
+  stage<kGroup>(rows, row0, n, kGroupObs, lane, slice, plane, out.bad);
+  __syncthreads();
+  if (!mine) return;
+  LaneTrack<kGroup, false, Rows> trk{n, lane, kGroupObs, plane, slice, rows, row0};
+  solve_and_store(trk, prm, t, out);
+}
+
+template <class Rows>
+__global__ __launch_bounds__(kWave) void tri_wave_kernel(Rows rows, const int64_t *__restrict__ offsets, const int32_t *__restrict__ long_tracks,
+                                                         Params prm, Out out) {
+  __shared__ double sh[6 * kWaveObs];
+  const int lane = (int)threadIdx.x;
+  const int64_t t = long_tracks[blockIdx.x];
+  const int64_t row0 = offsets[t];
+  const int n = (int)(offsets[t + 1] - row0);
+  stage<kWave>(rows, row0, n, kWaveObs, lane, sh, kWaveObs, out.bad);
+  __syncthreads();
+  LaneTrack<kWave, true, Rows> trk{n, lane, kWaveObs, kWaveObs, sh, rows, row0};
+  solve_and_store(trk, prm, t, out);
+}
+
+int check_args(const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p, const char *who) {
+  OSFM_REQUIRE(p, OSFM_E_INVALID, "%s: null params", who);
+  OSFM_REQUIRE(n_tracks >= 0, OSFM_E_INVALID, "%s: n_tracks < 0", who);
+  OSFM_REQUIRE(p->refinement_iterations >= 0, OSFM_E_INVALID, "%s: refinement_iterations < 0", who);
+  OSFM_REQUIRE(p->min_angle_deg >= 0.0 && p->min_angle_deg <= 180.0, OSFM_E_INVALID, "%s: min_angle_deg must lie in [0, 180]", who);
+  OSFM_REQUIRE(!(p->threshold != p->threshold) && !(p->min_depth != p->min_depth), OSFM_E_INVALID, "%s: threshold / min_depth is NaN", who);
+  if (n_tracks == 0) return OSFM_OK;
+  OSFM_REQUIRE(offsets, OSFM_E_INVALID, "%s: null track_offsets", who);
+  OSFM_REQUIRE(offsets[0] == 0, OSFM_E_INVALID, "%s: track_offsets[0] must be 0", who);
+  for (int t = 0; t < n_tracks; t++) {
+    OSFM_REQUIRE(offsets[t + 1] >= offsets[t], OSFM_E_INVALID, "%s: track_offsets decrease at track %d", who, t);
+    OSFM_REQUIRE(offsets[t + 1] - offsets[t] <= kMaxTrack, OSFM_E_UNSUPPORTED, "%s: track %d has more than 2^24 observations", who, t);
+  }
+  return OSFM_OK;
+}
+
+// Both kernels over rows that are on the device already; `uploaded` bytes of the arena hold the caller's inputs.  The caller holds the
+// context lock and has recorded nothing on ev[0] / ev[1].
+template <class Rows>
+int run_device(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p,
+               const double *initial, double *points, uint8_t *status, int32_t *iterations_used, double *kernel_ms, const char *who) {
+  std::vector<int32_t> long_tracks;
+  for (int t = 0; t < n_tracks; t++)
+    if (offsets[t + 1] - offsets[t] > kGroupObs) long_tracks.push_back(t);
+  const size_t n_long = long_tracks.size();
+  const size_t sizes[] = {((size_t)n_tracks + 1) * 8, n_long * 4, (size_t)n_tracks * 24, (size_t)n_tracks, (size_t)n_tracks * 4, 16,
+                          initial ? (size_t)n_tracks * 24 : 0};
+  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
+  size_t offs[kBuffers], arena_bytes = 0;
+  for (int i = 0; i < kBuffers; i++) {
+    offs[i] = arena_bytes;
+    arena_bytes += (sizes[i] + 255) / 256 * 256;
+  }
+  OsfmPoolBuf arena;
+  OSFM_HIP(arena.alloc(ctx, arena_bytes));
+  char *base = (char *)arena.p;
+  int64_t *d_off = (int64_t *)(base + offs[0]);
+  int32_t *d_long = (int32_t *)(base + offs[1]);
+  Out out{(double *)(base + offs[2]), (uint8_t *)(base + offs[3]), (int32_t *)(base + offs[4]), (int *)(base + offs[5]),
+          initial ? (const double *)(base + offs[6]) : nullptr};
+  if (initial) OSFM_HIP(hipMemcpyAsync(base + offs[6], initial, sizes[6], hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_off, offsets, sizes[0], hipMemcpyHostToDevice, st));
+  if (n_long) OSFM_HIP(hipMemcpyAsync(d_long, long_tracks.data(), sizes[1], hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemsetAsync(out.bad, 0, 16, st));
+  const Params prm{p->threshold, p->min_angle_deg * M_PI / 180.0, p->min_depth, (int)p->refinement_iterations};
+  OSFM_HIP(hipEventRecord(ctx->ev[0], st));
+  if (n_long < (size_t)n_tracks) {
+    hipLaunchKernelGGL((tri_group_kernel<Rows>), dim3((unsigned)((n_tracks + kGroupsPerBlock - 1) / kGroupsPerBlock)), dim3(kBlock), 0, st, rows,
+                       d_off, n_tracks, prm, out);
+    OSFM_HIP(hipGetLastError());
+  }
+  if (n_long) {
+    hipLaunchKernelGGL((tri_wave_kernel<Rows>), dim3((unsigned)n_long), dim3(kWave), 0, st, rows, d_off, d_long, prm, out);
+    OSFM_HIP(hipGetLastError());
+  }
+  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
+  int bad = 0;
+  OSFM_HIP(hipMemcpyAsync(&bad, out.bad, 4, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(points, out.points, sizes[2], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(status, out.status, sizes[3], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(iterations_used, out.iterations, sizes[4], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipStreamSynchronize(st));
+  if (kernel_ms) {
+    float ms = 0.f;
+    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    *kernel_ms = ms;
+  }
+  OSFM_REQUIRE(bad == 0, OSFM_E_INVALID, "%s: an observation names a shot outside the table, or it or its shot's pose is not finite", who);
+  return OSFM_OK;
+}
+
+}  // namespace
+
+extern "C" void osfm_triangulate_params_default(osfm_triangulate_params *p) {
+  if (!p) return;
+  p->threshold = 0.006;
+  p->min_angle_deg = 1.0;
+  p->min_depth = 0.001;
+  p->refinement_iterations = 10;
+  p->pad = 0;
+}
+
+static int bearings_call(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                         const osfm_triangulate_params *params, const double *initial_or_null, double *points, uint8_t *status,
+                         int32_t *iterations_used, double *kernel_ms, const char *who) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  if (n_tracks == 0) return OSFM_OK;
+  OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
+  const int64_t n_obs = track_offsets[n_tracks];
+  OSFM_REQUIRE(n_obs == 0 || (centers && bearings), OSFM_E_INVALID, "%s: null centers / bearings", who);
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  OsfmPoolBuf in;
+  const size_t bytes = ((size_t)n_obs * 24 + 255) / 256 * 256;
+  OSFM_HIP(in.alloc(ctx, 2 * bytes));
+  double *d_centers = (double *)in.p, *d_bearings = (double *)((char *)in.p + bytes);
+  if (n_obs) {
+    OSFM_HIP(hipMemcpyAsync(d_centers, centers, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
+    OSFM_HIP(hipMemcpyAsync(d_bearings, bearings, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
+  }
+  return run_device(ctx, st, BearingRows{d_centers, d_bearings}, track_offsets, n_tracks, params, initial_or_null, points, status, iterations_used, kernel_ms, who);
+}
+
+extern "C" int osfm_triangulate_tracks(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
+                                       const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy,
+                                       const int64_t *track_offsets, int n_tracks, const osfm_triangulate_params *params, double *points,
+                                       uint8_t *status, int32_t *iterations_used, double *kernel_ms) {
+  const char *who = "osfm_triangulate_tracks";
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  OSFM_REQUIRE(n_shots >= 0 && n_cams >= 0, OSFM_E_INVALID, "%s: negative size", who);
+  if (n_tracks == 0) return OSFM_OK;
+  OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
+  const int64_t n_obs = track_offsets[n_tracks];
+  OSFM_REQUIRE(n_obs == 0 || (shot_pose && shot_camera && cam_model && cam_params && obs_shot && obs_xy && n_shots > 0 && n_cams > 0),
+               OSFM_E_INVALID, "%s: null argument", who);
+  for (int c = 0; c < n_cams; c++)
+    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
+                 c, cam_model[c]);
+  for (int s = 0; s < n_shots; s++)
+    OSFM_REQUIRE(shot_camera[s] >= 0 && shot_camera[s] < n_cams, OSFM_E_INVALID, "%s: shot %d names a camera outside the table", who, s);
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t sizes[] = {(size_t)n_shots * 96, (size_t)n_shots * 4, (size_t)n_cams * 4, (size_t)n_cams * 128, (size_t)n_obs * 4, (size_t)n_obs * 16};
+  const void *src[] = {shot_pose, shot_camera, cam_model, cam_params, obs_shot, obs_xy};
+  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
+  size_t offs[kBuffers], arena_bytes = 0;
+  for (int i = 0; i < kBuffers; i++) {
+    offs[i] = arena_bytes;
+    arena_bytes += (sizes[i] + 255) / 256 * 256;
+  }
+  OsfmPoolBuf in;
+  OSFM_HIP(in.alloc(ctx, arena_bytes));
+  char *base = (char *)in.p;
+  for (int i = 0; i < kBuffers; i++)
+    if (sizes[i]) OSFM_HIP(hipMemcpyAsync(base + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st));
+  const PixelRows rows{(const double *)(base + offs[0]), (const int32_t *)(base + offs[1]), (const int32_t *)(base + offs[2]),
+                       (const double *)(base + offs[3]), (const int32_t *)(base + offs[4]), (const double *)(base + offs[5]), n_shots};
+  return run_device(ctx, st, rows, track_offsets, n_tracks, params, nullptr, points, status, iterations_used, kernel_ms, who);
+}
+
+extern "C" int osfm_triangulate_bearings(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                                         const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used,
+                                         double *kernel_ms) {
+  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, params, nullptr, points, status, iterations_used, kernel_ms,
+                       "osfm_triangulate_bearings");
+}
+
+extern "C" int osfm_triangulate_refine(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                                       const double *initial, int refinement_iterations, double *points, int32_t *iterations_used,
+                                       double *kernel_ms) {
+  const char *who = "osfm_triangulate_refine";
+  osfm_triangulate_params p;
+  osfm_triangulate_params_default(&p);
+  p.refinement_iterations = refinement_iterations;
+  OSFM_REQUIRE(n_tracks <= 0 || initial, OSFM_E_INVALID, "%s: null initial points", who);
+  std::vector<uint8_t> status((size_t)(n_tracks > 0 ? n_tracks : 0));
+  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, &p, n_tracks > 0 ? initial : nullptr, points, status.data(),
+                       iterations_used, kernel_ms, who);
+}

@@ -437,6 +437,35 @@ class Reconstruction:
             del self.shots[shot_id].observations[lm_id]
 
 
+class TracksManager:
+    """``pymap.TracksManager`` as far as triangulation reads it: observations by (shot, track), in insertion order"""
+
+    def __init__(self):
+        self._by_shot: Dict[str, Dict[str, Observation]] = {}
+        self._by_track: Dict[str, Dict[str, Observation]] = {}
+
+    def add_observation(self, shot_id: str, track_id: str, observation: Observation) -> None:
+        self._by_shot.setdefault(shot_id, {})[track_id] = observation
+        self._by_track.setdefault(track_id, {})[shot_id] = observation
+
+    def get_observation(self, shot_id: str, track_id: str) -> Observation:
+        return self._by_shot[shot_id][track_id]
+
+    def get_shot_ids(self) -> List[str]:
+        return list(self._by_shot)
+
+    def get_track_ids(self) -> List[str]:
+        return list(self._by_track)
+
+    def get_shot_observations(self, shot_id: str) -> Dict[str, Observation]:
+        """track id -> observation"""
+        return self._by_shot[shot_id]
+
+    def get_track_observations(self, track_id: str) -> Dict[str, Observation]:
+        """shot id -> observation"""
+        return self._by_track[track_id]
+
+
 def optional_value(x) -> Optional[Any]:
     """value of a reference ``OptionalValue`` (``.has_value`` / ``.value``), of a plain value, or None"""
     if x is None:

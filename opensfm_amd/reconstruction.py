@@ -6,17 +6,22 @@ normalised image coordinates in item order, computes the bearings and runs ``pyr
 one call, counts the rotation-only inliers and the reconstructability on the device, and sorts on the host exactly as the reference
 does (``np.argsort(-np.array(score))``).
 
+``triangulate_shot_features(tracks_manager, reconstruction, shot_ids, config)`` and ``retriangulate(tracks_manager, reconstruction, config)``
+(``reconstruction.py:1143-1226``) triangulate every track of their batch in one GPU call (``triangulate.hip``, ``triangulation_type: FULL``);
+``triangulate_bearings_arrays`` / ``triangulate_tracks_arrays`` are the same call on flat arrays.
+
 ``cull_final_point_cloud(reconstruction, config)`` is the tail of ``grow_reconstruction`` after its last bundle
 (``reconstruction.py:1586-1594``): the outlier step (``discard_gross_observations``) and, under ``filter_final_point_cloud``, the two point-cloud filters on the GPU
 (``cloud.hip``)."""
 from __future__ import annotations
 
 import ctypes as C
+import time
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import RelrotParams, RelrotResult, check, default_context, load
+from ._lib import RelrotParams, RelrotResult, TriangulateParams, check, default_context, load
 from .matching import camera_parameters
 
 
@@ -192,4 +197,156 @@ def cull_final_point_cloud(reconstruction, config: Dict[str, Any]) -> Dict[str, 
     if config["filter_final_point_cloud"]:
         report["badly_conditioned"] = opensfm_adapter.filter_badly_conditioned_points(reconstruction.map, config["triangulation_min_ray_angle"])
         report["isolated"] = opensfm_adapter.remove_isolated_points(reconstruction.map)
+    return report
+
+
+# ------------------------------------------------------------------------------------------------
+# triangulation of tracks (reconstruction.py:1032-1226)
+# ------------------------------------------------------------------------------------------------
+TRIANGULATION_STATUS = ("triangulated", "fewer than 2 observations", "ray angle", "reprojection angle", "depth", "result not finite")
+
+
+def _triangulate_params(threshold: float, min_angle_deg: float, min_depth: float, refinement_iterations: int) -> TriangulateParams:
+    return TriangulateParams(float(threshold), float(min_angle_deg), float(min_depth), int(refinement_iterations), 0)
+
+
+def _triangulate_outputs(n_tracks: int):
+    return np.full((max(n_tracks, 1), 3), np.nan), np.zeros(max(n_tracks, 1), np.uint8), np.zeros(max(n_tracks, 1), np.int32), C.c_double(0.0)
+
+
+def triangulate_bearings_arrays(centers: np.ndarray, bearings: np.ndarray, track_offsets: Sequence[int], threshold: float = 0.006,
+                                min_angle_deg: float = 1.0, min_depth: float = 0.001, refinement_iterations: int = 10,
+                                ctx=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+    """``osfm_triangulate_bearings``: track t owns rows track_offsets[t]:track_offsets[t+1] of centers / bearings (world coordinates).
+    -> (points (n, 3), NaN unless triangulated; status (n,), see TRIANGULATION_STATUS; TinySolver iterations (n,); kernel milliseconds)."""
+    ctx = ctx or default_context()
+    centers = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+    bearings = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(track_offsets, np.int64)
+    n_tracks = len(off) - 1
+    if len(centers) != len(bearings) or n_tracks < 0 or (n_tracks > 0 and off[-1] != len(centers)):
+        raise ValueError("triangulate_bearings_arrays: centers / bearings / track_offsets do not agree")
+    prm = _triangulate_params(threshold, min_angle_deg, min_depth, refinement_iterations)
+    points, status, iterations, ms = _triangulate_outputs(n_tracks)
+    check(load().osfm_triangulate_bearings(ctx.handle, _fptr(centers, C.c_double), _fptr(bearings, C.c_double), _fptr(off, C.c_int64), n_tracks,
+                                           C.byref(prm), _fptr(points, C.c_double), _fptr(status, C.c_uint8), _fptr(iterations, C.c_int32),
+                                           C.byref(ms)), "osfm_triangulate_bearings")
+    return points[:n_tracks], status[:n_tracks], iterations[:n_tracks], ms.value
+
+
+def triangulate_tracks_arrays(shot_pose: np.ndarray, shot_camera: np.ndarray, cam_model: np.ndarray, cam_params: np.ndarray,
+                              obs_shot: np.ndarray, obs_xy: np.ndarray, track_offsets: Sequence[int], threshold: float = 0.006,
+                              min_angle_deg: float = 1.0, min_depth: float = 0.001, refinement_iterations: int = 10,
+                              ctx=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, float]:
+    """``osfm_triangulate_tracks``: the same from (shot, normalised image point) rows; shot_pose (n_shots, 12) holds R (row-major) then t
+    of every shot's world-to-camera pose composed with its rig, cam_params (n_cams, 16) the cameras in the native parameter order."""
+    ctx = ctx or default_context()
+    shot_pose = np.ascontiguousarray(shot_pose, np.float64).reshape(-1, 12)
+    shot_camera = np.ascontiguousarray(shot_camera, np.int32)
+    cam_model = np.ascontiguousarray(cam_model, np.int32)
+    cam_params = np.ascontiguousarray(cam_params, np.float64).reshape(-1, 16)
+    obs_shot = np.ascontiguousarray(obs_shot, np.int32)
+    obs_xy = np.ascontiguousarray(np.asarray(obs_xy, np.float64).reshape(-1, 2))
+    off = np.ascontiguousarray(track_offsets, np.int64)
+    n_tracks = len(off) - 1
+    if (len(shot_camera) != len(shot_pose) or len(cam_params) != len(cam_model) or len(obs_shot) != len(obs_xy) or n_tracks < 0
+            or (n_tracks > 0 and off[-1] != len(obs_shot))):
+        raise ValueError("triangulate_tracks_arrays: array lengths do not agree")
+    prm = _triangulate_params(threshold, min_angle_deg, min_depth, refinement_iterations)
+    points, status, iterations, ms = _triangulate_outputs(n_tracks)
+    check(load().osfm_triangulate_tracks(ctx.handle, _fptr(shot_pose, C.c_double), _fptr(shot_camera, C.c_int32), len(shot_pose),
+                                         _fptr(cam_model, C.c_int32), _fptr(cam_params, C.c_double), len(cam_model), _fptr(obs_shot, C.c_int32),
+                                         _fptr(obs_xy, C.c_double), _fptr(off, C.c_int64), n_tracks, C.byref(prm), _fptr(points, C.c_double),
+                                         _fptr(status, C.c_uint8), _fptr(iterations, C.c_int32), C.byref(ms)), "osfm_triangulate_tracks")
+    return points[:n_tracks], status[:n_tracks], iterations[:n_tracks], ms.value
+
+
+def _triangulate_into(tracks_manager, reconstruction, track_ids: List[str], config: Dict[str, Any], ctx=None) -> None:
+    """TrackTriangulator.triangulate for every track of `track_ids` in one call: the observations of a track in the shots of the
+    reconstruction, in the order the manager returns them; every accepted track becomes a point that all of them observe."""
+    threshold = config["triangulation_threshold"]
+    min_ray_angle = config["triangulation_min_ray_angle"]
+    min_depth = config["triangulation_min_depth"]
+    refinement_iterations = config["triangulation_refinement_iterations"]
+    kind = config["triangulation_type"]
+    if kind == "ROBUST":
+        raise NotImplementedError("triangulation_type ROBUST draws from numpy's global generator over an unordered set of tracks: it has no "
+                                  "reproducible result, and the GPU path implements FULL only")
+    if kind != "FULL" or not track_ids:  # (the reference does nothing for any other value)
+        return
+    shots = reconstruction.shots
+    shot_index: Dict[str, int] = {}
+    cam_index: Dict[str, int] = {}
+    poses: List[np.ndarray] = []
+    shot_camera: List[int] = []
+    models: List[int] = []
+    params: List[np.ndarray] = []
+    obs_shot: List[int] = []
+    obs_xy: List[Any] = []
+    members: List[List[str]] = []
+    for track in track_ids:
+        ids = []
+        for shot_id, obs in tracks_manager.get_track_observations(track).items():
+            if shot_id not in shots:
+                continue
+            s = shot_index.get(shot_id)
+            if s is None:
+                shot = shots[shot_id]
+                cam = shot.camera
+                if cam.id not in cam_index:
+                    model, par = camera_parameters(cam)
+                    cam_index[cam.id] = len(models)
+                    models.append(model)
+                    params.append(par)
+                pose = shot.pose
+                poses.append(np.r_[np.asarray(pose.get_rotation_matrix(), float).reshape(9), np.asarray(pose.translation, float).reshape(3)])
+                shot_camera.append(cam_index[cam.id])
+                s = shot_index[shot_id] = len(poses) - 1
+            obs_shot.append(s)
+            obs_xy.append(obs.point)
+            ids.append(shot_id)
+        members.append(ids)
+    offsets = np.r_[0, np.cumsum([len(m) for m in members])].astype(np.int64)
+    if not poses:  # no track has an observation in the reconstruction
+        return
+    points, status, _, _ = triangulate_tracks_arrays(np.array(poses), np.array(shot_camera, np.int32), np.array(models, np.int32),
+                                                     np.array(params, np.float64).reshape(-1, 16), np.array(obs_shot, np.int32),
+                                                     np.array(obs_xy, np.float64).reshape(-1, 2), offsets, threshold, min_ray_angle, min_depth,
+                                                     refinement_iterations, ctx=ctx)
+    for track, ids, X, st in zip(track_ids, members, points, status):
+        if st != 0:
+            continue
+        reconstruction.create_point(track, X.tolist())
+        for shot_id in ids:
+            reconstruction.add_observation(shot_id, track, tracks_manager.get_observation(shot_id, track))
+
+
+def triangulate_shot_features(tracks_manager, reconstruction, shot_ids, config: Dict[str, Any], ctx=None) -> None:
+    """Reconstruct as many tracks seen in `shot_ids` as possible (``reconstruction.py:1143-1183``): the tracks of those shots that the
+    reconstruction does not hold yet, one GPU call.  ``triangulation_type`` FULL; ROBUST raises NotImplementedError."""
+    all_shots_ids = set(tracks_manager.get_shot_ids())
+    tracks_ids = dict.fromkeys(t for s in shot_ids if s in all_shots_ids for t in tracks_manager.get_shot_observations(s))
+    _triangulate_into(tracks_manager, reconstruction, [t for t in tracks_ids if t not in reconstruction.points], config, ctx)
+
+
+def retriangulate(tracks_manager, reconstruction, config: Dict[str, Any], ctx=None) -> Dict[str, Any]:
+    """Retriangulate all points (``reconstruction.py:1186-1226``): the map's points are dropped and every track seen by its shots goes
+    through one GPU call.  -> {"num_points_before", "num_points_after", "wall_time"}"""
+    start = time.perf_counter()
+    report: Dict[str, Any] = {"num_points_before": len(reconstruction.points)}
+    for key in ("triangulation_threshold", "triangulation_min_ray_angle", "triangulation_min_depth", "triangulation_refinement_iterations"):
+        config[key]  # read before the map is touched, as the reference does
+    if config["triangulation_type"] == "ROBUST":
+        _triangulate_into(tracks_manager, reconstruction, [], config, ctx)  # raises
+    if hasattr(reconstruction, "remove_landmark"):
+        for lm_id in list(reconstruction.points):
+            reconstruction.remove_landmark(lm_id)
+    else:
+        reconstruction.points = {}
+    all_shots_ids = set(tracks_manager.get_shot_ids())
+    tracks = dict.fromkeys(t for image in reconstruction.shots.keys() if image in all_shots_ids
+                           for t in tracks_manager.get_shot_observations(image).keys())
+    _triangulate_into(tracks_manager, reconstruction, list(tracks), config, ctx)
+    report["num_points_after"] = len(reconstruction.points)
+    report["wall_time"] = time.perf_counter() - start
     return report
