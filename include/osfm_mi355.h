@@ -479,6 +479,55 @@ int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, 
                              const int32_t *cam_model, const double *cam_params, int n_cams, const osfm_relrot_params *params,
                              osfm_relrot_result *results, uint8_t *mask_or_null, double *kernel_ms /* may be NULL */);
 
+/* =====================================================================================
+ * Absolute-pose (P3P) LO-RANSAC of candidate images (reconstruction.resect, opensfm/reconstruction.py:695-762): the step of
+ * grow_reconstruction that adds an image to the map.  abspose.hip / abspose_core.h: one wavefront per image (lane 0 draws the next
+ * block of samples, four lanes per sample solve one root of the three-point solver's quartic each, the wavefront scores every model
+ * over the image's rows in the reference's order; the Lu-Hager solves of a local optimisation run one per lane); the same launch
+ * applies resect's inlier test.  The decision path uses + - * / sqrt only (the quartic's complex square and cube roots included), so
+ * the walk is pinned bit for bit by a host build of the same header (tests/test_abspose_host.py) against a sequential restatement
+ * on std::mt19937 and against the reference's robust_estimator.h; the GPU is pinned against that host build
+ * (tests/test_gpu_abspose.py).  What is not pinned: Eigen's and libstdc++'s last bits (abspose_core.h says which).
+ *
+ * osfm_abspose_images   pyrobust.ransac_absolute_pose(bearings, points, threshold, params, RANSAC) for every image of a batch
+ *   (robust/src/instanciations.cc:67-83 -> Estimate<RansacScoring, AbsolutePose>): image i owns the rows offsets[i] .. offsets[i+1]-1
+ *   of bearings / points (total x 3).  Sampler std::mt19937(42), 0 or 4 models per sample scored in order, ties keep the newcomer, LO
+ *   on every new or tied best with >= 3 inliers, ShouldStop with exponent 3 after every model.
+ *   result.model / lo_model: ScoreInfo::model / lo_model ([R | t], 3 x 4 row-major; all zero when no sample gave a model); score;
+ *   iterations run.  ransac_mask (total bytes, may be NULL): the inliers of the best score.
+ *   params.inlier_chord > 0: resect's test on T = [R^T | -R^T t] of lo_model (multiview.absolute_pose_ransac):
+ *   |normalized(R (X - o)) - b| < chord -> num_inliers and chord_mask (total bytes, may be NULL); <= 0: num_inliers = -1, mask zero.
+ *   n_images == 0 returns OSFM_OK and touches nothing.  An image with fewer than 3 rows is OSFM_E_INVALID: the reference's sampler
+ *   never returns there (resect itself returns before the call below 5 rows).
+ * osfm_abspose_images_pixels   the same from normalised image coordinates xy (total x 2): the bearings are computed on the device
+ *   with camera image_cam[i] of the table cam_model[n_cams] (OSFM_CAMERA_*) / cam_params[n_cams x 16].  kernel_ms includes them.
+ * osfm_abspose_solve   the leaf solvers: kind 0 = geometry.absolute_pose_three_points on rows 0 .. 2 (models_out: 4 x 12, *count_out
+ *   0 or 4; models [R^T | -R^T t] as the reference returns them), kind 1 = geometry.absolute_pose_n_points on all n rows
+ *   (models_out: 12, *count_out = 1).
+ * ===================================================================================== */
+typedef struct osfm_abspose_params {
+  double threshold;                /* radians: config resection_threshold in resect (0.004) */
+  double probability;              /* RobustEstimatorParams::probability (0.99: absolute_pose_ransac never sets it) */
+  double inlier_chord;             /* chord of resect's inlier test (resect: the threshold); <= 0: skipped */
+  int32_t iterations;              /* 1000 (reconstruction.py:725) */
+  int32_t use_lo;                  /* RobustEstimatorParams::use_local_optimization (1) */
+  int32_t lo_iterations;           /* ::local_optimization_iterations (10) */
+  int32_t use_iteration_reduction; /* ::use_iteration_reduction (1) */
+} osfm_abspose_params;
+typedef struct osfm_abspose_result {
+  double model[12], lo_model[12];      /* ScoreInfo::model / lo_model, 3 x 4 row-major */
+  int32_t score, iterations;           /* best inlier count, iterations run */
+  int32_t num_inliers;                 /* resect's inliers; -1 when skipped */
+} osfm_abspose_result;
+int osfm_abspose_images(osfm_ctx *ctx, const double *bearings, const double *points, const int64_t *offsets, int n_images,
+                        const osfm_abspose_params *params, osfm_abspose_result *results, uint8_t *ransac_mask_or_null,
+                        uint8_t *chord_mask_or_null, double *kernel_ms /* may be NULL: HIP-event time */);
+int osfm_abspose_images_pixels(osfm_ctx *ctx, const double *xy, const double *points, const int64_t *offsets, int n_images,
+                               const int32_t *image_cam, const int32_t *cam_model, const double *cam_params, int n_cams,
+                               const osfm_abspose_params *params, osfm_abspose_result *results, uint8_t *ransac_mask_or_null,
+                               uint8_t *chord_mask_or_null, double *kernel_ms /* may be NULL */);
+int osfm_abspose_solve(osfm_ctx *ctx, const double *bearings, const double *points, int n, int kind, double *models_out, int *count_out);
+
 /*
  * Batched pair matching for the pairs that take the calibrated branch of robust_match (opensfm/matching.py:906-929: every pair with
  * a camera that is not an undistorted perspective / brown one): per pair matching.match (matching.py:563-634) = descriptor stage,

@@ -77,6 +77,19 @@ class RelrotResult(C.Structure):
     ]
 
 
+AbsposeParams = RelrotParams  # osfm_abspose_params has the fields of osfm_relrot_params
+
+
+class AbsposeResult(C.Structure):
+    _fields_ = [
+        ("model", C.c_double * 12),
+        ("lo_model", C.c_double * 12),
+        ("score", C.c_int32),
+        ("iterations", C.c_int32),
+        ("num_inliers", C.c_int32),
+    ]
+
+
 class TriangulateParams(C.Structure):
     _fields_ = [
         ("threshold", C.c_double),
@@ -176,6 +189,19 @@ SIGNATURES = {
         [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
          C.POINTER(C.c_double), C.c_int, C.POINTER(RelrotParams), C.POINTER(RelrotResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
     ),
+    "osfm_abspose_images": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(AbsposeParams),
+         C.POINTER(AbsposeResult), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_abspose_images_pixels": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(C.c_double), C.c_int, C.POINTER(AbsposeParams), C.POINTER(AbsposeResult), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+         C.POINTER(C.c_double)],
+    ),
+    "osfm_abspose_solve": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int)]),
     "osfm_points_conditioning": (
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double),

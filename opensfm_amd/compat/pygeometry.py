@@ -1,11 +1,12 @@
-"""Two leaves of the reference's ``pygeometry`` (``opensfm/src/geometry/python/pybind.cc:298,309``) under its argument names, served by
-``triangulate.hip``: ``triangulate_bearings_midpoint`` and ``point_refinement``.  One call is one track on the GPU -- these exist so that
+"""Leaves of the reference's ``pygeometry`` (``opensfm/src/geometry/python/pybind.cc``) under its argument names:
+``triangulate_bearings_midpoint`` and ``point_refinement``, served by ``triangulate.hip``, and ``absolute_pose_three_points`` and
+``absolute_pose_n_points``, served by ``abspose.hip``.  One call is one track on the GPU -- these exist so that
 code written against the leaves (``TrackTriangulator``) runs unchanged; the batched path is
 ``opensfm_amd.reconstruction.triangulate_shot_features`` / ``retriangulate``.
 
 This module is NOT registered by ``compat.install()`` (``compat.MODULES`` stays as it is): import it directly,
 ``from opensfm_amd.compat import pygeometry``."""
-from typing import Sequence, Tuple
+from typing import List, Sequence, Tuple
 
 import numpy as np
 
@@ -53,3 +54,30 @@ def point_refinement(centers, bearings, point, iterations: int) -> np.ndarray:
                                            ptr(initial, C.c_double), int(iterations), ptr(out, C.c_double), ptr(used, C.c_int32), C.byref(ms)),
            "osfm_triangulate_refine")
     return out
+
+
+def _abspose_solve(bearings, points, kind: int, who: str):
+    import ctypes as C
+
+    bearings = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    if len(bearings) != len(points):
+        raise ValueError(f"{who}: bearings and points do not agree")
+    models, count = np.zeros((4, 3, 4)), C.c_int(0)
+    _check(_load().osfm_abspose_solve(_default_context().handle, bearings.ctypes.data_as(C.POINTER(C.c_double)),
+                                      points.ctypes.data_as(C.POINTER(C.c_double)), len(bearings), kind,
+                                      models.ctypes.data_as(C.POINTER(C.c_double)), C.byref(count)), "osfm_abspose_solve")
+    return models, count.value
+
+
+def absolute_pose_three_points(bearings, points) -> List[np.ndarray]:
+    """``geometry::AbsolutePoseThreePoints`` (absolute_pose.h:15-122) on the first three rows: no model or four 3 x 4 models
+    [R^T | -R^T t] (a model whose root of the quartic lies outside [-1, 1] is NaN, as in the reference)"""
+    models, count = _abspose_solve(bearings, points, 0, "absolute_pose_three_points")
+    return [models[i].copy() for i in range(count)]
+
+
+def absolute_pose_n_points(bearings, points) -> np.ndarray:
+    """``geometry::AbsolutePoseNPoints`` (absolute_pose.h:144-189): the 3 x 4 model [R | t] of the Lu-Hager iteration over all rows"""
+    models, _ = _abspose_solve(bearings, points, 1, "absolute_pose_n_points")
+    return models[0].copy()

@@ -1,7 +1,9 @@
 """``pyrobust`` (opensfm/src/robust/python/pybind.cc:26-56): ``ransac_relative_pose`` -- the estimator of the calibrated robust-matching
 branch (robust/src/instanciations.cc:33-48) -- and ``ransac_relative_rotation`` -- the estimator that ranks the initial pairs of
-``reconstruct`` (instanciations.cc:50-64, through multiview.relative_pose_ransac_rotation_only) -- with ``RobustEstimatorParams`` and
-``RansacType``.  The other estimators of the reference's module (line, essential, absolute pose, similarity) are not provided."""
+``reconstruct`` (instanciations.cc:50-64, through multiview.relative_pose_ransac_rotation_only) -- and ``ransac_absolute_pose`` -- the
+estimator of ``resect`` (instanciations.cc:67-83, through multiview.absolute_pose_ransac) -- with ``RobustEstimatorParams`` and
+``RansacType``.  The other estimators of the reference's module (line, essential, absolute pose with known rotation, similarity) are
+not provided."""
 import enum
 
 import numpy as np
@@ -79,6 +81,28 @@ def ransac_relative_rotation(b1, b2, threshold: float, parameters: RobustEstimat
                                                 probability=parameters.probability, use_lo=parameters.use_local_optimization,
                                                 lo_iterations=getattr(parameters, "local_optimization_iterations", 10))
     out = ScoreInfoMatrix3d()
+    out.score, out.model, out.lo_model = float(res[0]["score"]), res[0]["model"], res[0]["lo_model"]
+    out.inliers_indices = [int(i) for i in np.flatnonzero(mask)]
+    return out
+
+
+def ransac_absolute_pose(bearings, points, threshold: float, parameters: RobustEstimatorParams, ransac_type: RansacType = RansacType.RANSAC):
+    """robust::RANSACAbsolutePose: LO-RANSAC of the camera pose from bearings and points (n x 3 each, n >= 3); ScoreInfo with the 3 x 4
+    model [R | t] (world to camera)"""
+    if int(ransac_type) != int(RansacType.RANSAC):
+        raise NotImplementedError("only RansacType.RANSAC is on the GPU path (what multiview.absolute_pose_ransac asks for)")
+    if not parameters.use_iteration_reduction:
+        raise NotImplementedError("use_iteration_reduction = False is not on the GPU path")
+    bearings, points = np.asarray(bearings, np.float64).reshape(-1, 3), np.asarray(points, np.float64).reshape(-1, 3)
+    if len(bearings) != len(points):
+        raise RuntimeError("Features matrices have different sizes.")  # instanciations.cc:71-73
+    from .. import reconstruction as _reconstruction
+
+    res, mask, _, _ = _reconstruction.abspose_images(bearings, points, [0, len(bearings)], threshold, iterations=parameters.iterations,
+                                                     probability=parameters.probability, use_lo=parameters.use_local_optimization,
+                                                     lo_iterations=getattr(parameters, "local_optimization_iterations", 10),
+                                                     inlier_chord=0.0)
+    out = ScoreInfoMatrix34d()
     out.score, out.model, out.lo_model = float(res[0]["score"]), res[0]["model"], res[0]["lo_model"]
     out.inliers_indices = [int(i) for i in np.flatnonzero(mask)]
     return out

@@ -160,17 +160,32 @@ OSFM_HD void jacobi_svd3(const double* A, double* U, double* S, double* V) {
   }
 }
 
-// RotationBetweenPoints over the correspondences idx[0 .. count-1] (first = b1, second = b2), transposed: the RelativeRotation model
-// (row-major).  Operation order: centroids = sum in sample order, then / count; M(i, j) = sum over the sample (from 0.0) of
-// q_i p_j with q = first - centroid, p = second - centroid; R = U V^T (3-term sums left to right); det R < 0: R = -R.
-// negated (optional): set to whether the det R < 0 branch was taken.
-OSFM_HD void rotation_model(const double* b1, const double* b2, const int* idx, int count, double* model, int* negated = nullptr) {
+// ClosestRotationMatrix (foundation/src/numeric.cc:11-19) and the tail of RotationBetweenPoints: R = U V^T (3-term sums left to right),
+// the WHOLE matrix negated when det R < 0.  R row-major; negated (optional): whether that branch was taken.
+OSFM_HD void closest_rotation(const double* M, double* R, int* negated = nullptr) {
+  double U[9], S[3], V[9];
+  jacobi_svd3(M, U, S, V);
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) R[3 * i + j] = U[3 * i] * V[3 * j] + U[3 * i + 1] * V[3 * j + 1] + U[3 * i + 2] * V[3 * j + 2];
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
+  const double sign = det < 0.0 ? -1.0 : 1.0;
+  if (negated) *negated = det < 0.0;
+  for (int i = 0; i < 9; i++) R[i] = R[i] * sign;
+}
+
+// RotationBetweenPoints (geometry/transform.h:21-40) over `count` pairs; first(k, v) / second(k, v) write the two vectors of pair k to v[3]
+// (they are called twice per pair: once for the centroids, once for M).  Operation order: centroids = sum in order, then / count;
+// M(i, j) = sum over the pairs (from 0.0) of q_i p_j with q = first - centroid, p = second - centroid; closest_rotation(M).  Not transposed.
+template <class FA, class FB>
+OSFM_HD void rotation_between_points(FA first, FB second, int count, double* R, int* negated = nullptr) {
   double qa[3] = {0.0, 0.0, 0.0}, pa[3] = {0.0, 0.0, 0.0};
   for (int k = 0; k < count; k++) {
-    const int m = idx[k];
+    double q[3], p[3];
+    first(k, q);
+    second(k, p);
     for (int a = 0; a < 3; a++) {
-      qa[a] += b1[3 * m + a];
-      pa[a] += b2[3 * m + a];
+      qa[a] += q[a];
+      pa[a] += p[a];
     }
   }
   for (int a = 0; a < 3; a++) {
@@ -180,24 +195,32 @@ OSFM_HD void rotation_model(const double* b1, const double* b2, const int* idx, 
   double M[9];
   for (int i = 0; i < 9; i++) M[i] = 0.0;
   for (int k = 0; k < count; k++) {
-    const int m = idx[k];
     double q[3], p[3];
+    first(k, q);
+    second(k, p);
     for (int a = 0; a < 3; a++) {
-      q[a] = b1[3 * m + a] - qa[a];
-      p[a] = b2[3 * m + a] - pa[a];
+      q[a] = q[a] - qa[a];
+      p[a] = p[a] - pa[a];
     }
     for (int i = 0; i < 3; i++)
       for (int j = 0; j < 3; j++) M[3 * i + j] += q[i] * p[j];
   }
-  double U[9], S[3], V[9], R[9];
-  jacobi_svd3(M, U, S, V);
+  closest_rotation(M, R, negated);
+}
+
+// RotationBetweenPoints over the correspondences idx[0 .. count-1] (first = b1, second = b2), transposed: the RelativeRotation model
+// (row-major).  negated (optional): set to whether the det R < 0 branch was taken.
+OSFM_HD void rotation_model(const double* b1, const double* b2, const int* idx, int count, double* model, int* negated = nullptr) {
+  double R[9];
+  auto first = [=](int k, double* v) {
+    for (int a = 0; a < 3; a++) v[a] = b1[3 * idx[k] + a];
+  };
+  auto second = [=](int k, double* v) {
+    for (int a = 0; a < 3; a++) v[a] = b2[3 * idx[k] + a];
+  };
+  rotation_between_points(first, second, count, R, negated);
   for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) R[3 * i + j] = U[3 * i] * V[3 * j] + U[3 * i + 1] * V[3 * j + 1] + U[3 * i + 2] * V[3 * j + 2];
-  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[3] * (R[1] * R[8] - R[7] * R[2]) + R[6] * (R[1] * R[5] - R[4] * R[2]);
-  const double sign = det < 0.0 ? -1.0 : 1.0;
-  if (negated) *negated = det < 0.0;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) model[3 * i + j] = R[3 * j + i] * sign;
+    for (int j = 0; j < 3; j++) model[3 * i + j] = R[3 * j + i];
 }
 
 // RelativeRotation::Evaluate: e = 1 - (model first) . second; RansacScoring: an inlier when |e| < thr (= 1 - cos(threshold))

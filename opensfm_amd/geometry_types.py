@@ -318,6 +318,13 @@ class RigInstance:
         self.shots: Dict[str, Shot] = {}
         self.rig_camera_ids: Dict[str, str] = {}
 
+    def update_instance_pose_with_shot(self, shot_id: str, shot_pose: Pose) -> None:
+        """``RigInstance::UpdateInstancePoseWithShot`` (map/src/rig.cc:37-50): pose(shot) = pose(rig camera) o pose(instance), so the
+        instance pose that gives `shot_id` the pose `shot_pose` is pose(rig camera)^-1 o shot_pose"""
+        if shot_id not in self.shots:
+            raise RuntimeError("Cannot find " + shot_id + " in RigInstance")
+        self.pose = self.shots[shot_id].rig_camera.pose.inverse().compose(shot_pose)
+
 
 class Landmark:
     def __init__(self, landmark_id: str, coordinates):

@@ -10,6 +10,11 @@ does (``np.argsort(-np.array(score))``).
 (``reconstruction.py:1143-1226``) triangulate every track of their batch in one GPU call (``triangulate.hip``, ``triangulation_type: FULL``);
 ``triangulate_bearings_arrays`` / ``triangulate_tracks_arrays`` are the same call on flat arrays.
 
+``resect(data, tracks_manager, reconstruction, shot_id, threshold, min_inliers)`` (``reconstruction.py:695-762``) adds one image to the map
+with the absolute-pose LO-RANSAC of ``abspose.hip``; ``resect_candidates`` is the candidate loop of ``grow_reconstruction``
+(``:1525-1575``) with up to ``max_batch`` candidates solved per GPU call; ``abspose_images`` / ``abspose_images_pixels`` are the same
+estimator on flat arrays and ``absolute_pose_ransac`` is ``multiview.absolute_pose_ransac``.
+
 ``cull_final_point_cloud(reconstruction, config)`` is the tail of ``grow_reconstruction`` after its last bundle
 (``reconstruction.py:1586-1594``): the outlier step (``discard_gross_observations``) and, under ``filter_final_point_cloud``, the two point-cloud filters on the GPU
 (``cloud.hip``)."""
@@ -17,11 +22,11 @@ from __future__ import annotations
 
 import ctypes as C
 import time
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
-from ._lib import RelrotParams, RelrotResult, TriangulateParams, check, default_context, load
+from ._lib import AbsposeParams, AbsposeResult, RelrotParams, RelrotResult, TriangulateParams, check, default_context, load
 from .matching import camera_parameters
 
 
@@ -350,3 +355,231 @@ def retriangulate(tracks_manager, reconstruction, config: Dict[str, Any], ctx=No
     report["num_points_after"] = len(reconstruction.points)
     report["wall_time"] = time.perf_counter() - start
     return report
+
+
+# ------------------------------------------------------------------------------------------------
+# resection of candidate images (reconstruction.py:677-762, 1525-1575)
+# ------------------------------------------------------------------------------------------------
+def _abspose_params(threshold: float, iterations: int, probability: float, use_lo: bool, lo_iterations: int, use_iteration_reduction: bool,
+                    inlier_chord: Optional[float]) -> AbsposeParams:
+    chord = threshold if inlier_chord is None else inlier_chord
+    return AbsposeParams(float(threshold), float(probability), float(chord), int(iterations), int(bool(use_lo)), int(lo_iterations),
+                         int(bool(use_iteration_reduction)))
+
+
+def _abspose_results(res, n_images: int) -> List[Dict[str, Any]]:
+    return [{"model": np.array(res[i].model).reshape(3, 4), "lo_model": np.array(res[i].lo_model).reshape(3, 4), "score": res[i].score,
+             "iterations": res[i].iterations, "num_inliers": res[i].num_inliers} for i in range(n_images)]
+
+
+def abspose_images(bearings: np.ndarray, points: np.ndarray, offsets: Sequence[int], threshold: float, iterations: int = 1000,
+                   probability: float = 0.99, use_lo: bool = True, lo_iterations: int = 10, use_iteration_reduction: bool = True,
+                   inlier_chord: Optional[float] = None, ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, np.ndarray, float]:
+    """Batched ``pyrobust.ransac_absolute_pose`` on bearings and points (``osfm_abspose_images``): image i owns rows
+    offsets[i]:offsets[i+1].  ``inlier_chord``: the chord of ``resect``'s inlier test on the inverted lo_model (default: the threshold;
+    <= 0 skips it).  -> (per-image dicts, mask of the RANSAC inliers, mask of resect's inliers, kernel milliseconds)."""
+    ctx = ctx or default_context()
+    b = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    X = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_images = len(off) - 1
+    if len(b) != len(X) or n_images < 0 or (n_images > 0 and off[-1] != len(b)):
+        raise ValueError("abspose_images: bearings / points / offsets do not agree")
+    prm = _abspose_params(threshold, iterations, probability, use_lo, lo_iterations, use_iteration_reduction, inlier_chord)
+    res = (AbsposeResult * max(n_images, 1))()
+    rmask, cmask = np.zeros(max(len(b), 1), np.uint8), np.zeros(max(len(b), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_abspose_images(ctx.handle, _fptr(b, C.c_double), _fptr(X, C.c_double), _fptr(off, C.c_int64), n_images, C.byref(prm), res,
+                                     _fptr(rmask, C.c_uint8), _fptr(cmask, C.c_uint8), C.byref(ms)), "osfm_abspose_images")
+    return _abspose_results(res, n_images), rmask[: len(b)].astype(bool), cmask[: len(b)].astype(bool), ms.value
+
+
+def abspose_images_pixels(xy: np.ndarray, points: np.ndarray, offsets: Sequence[int], image_cam: np.ndarray, cam_model: np.ndarray,
+                          cam_params: np.ndarray, threshold: float, iterations: int = 1000, probability: float = 0.99, use_lo: bool = True,
+                          lo_iterations: int = 10, use_iteration_reduction: bool = True, inlier_chord: Optional[float] = None,
+                          ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, np.ndarray, float]:
+    """``osfm_abspose_images_pixels``: the same from normalised image coordinates, the bearings computed on the device with camera
+    image_cam[i] of the table cam_model (n_cams) / cam_params (n_cams x 16)."""
+    ctx = ctx or default_context()
+    xy = np.ascontiguousarray(np.asarray(xy, np.float64).reshape(-1, 2))
+    X = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_images = len(off) - 1
+    if len(xy) != len(X) or n_images < 0 or (n_images > 0 and off[-1] != len(xy)):
+        raise ValueError("abspose_images_pixels: xy / points / offsets do not agree")
+    ic = np.ascontiguousarray(image_cam, np.int32)
+    cm = np.ascontiguousarray(cam_model, np.int32)
+    cp = np.ascontiguousarray(cam_params, np.float64)
+    if ic.shape != (n_images,) or cm.ndim != 1 or cp.shape != (len(cm), 16):
+        raise ValueError(f"abspose_images_pixels: image_cam must be ({n_images},) and cam_params ({len(cm)}, 16) for cam_model of length "
+                         f"{len(cm)}; got {ic.shape}, {cp.shape}")
+    prm = _abspose_params(threshold, iterations, probability, use_lo, lo_iterations, use_iteration_reduction, inlier_chord)
+    res = (AbsposeResult * max(n_images, 1))()
+    rmask, cmask = np.zeros(max(len(xy), 1), np.uint8), np.zeros(max(len(xy), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_abspose_images_pixels(ctx.handle, _fptr(xy, C.c_double), _fptr(X, C.c_double), _fptr(off, C.c_int64), n_images,
+                                            _fptr(ic, C.c_int32), _fptr(cm, C.c_int32), _fptr(cp, C.c_double), len(cm), C.byref(prm), res,
+                                            _fptr(rmask, C.c_uint8), _fptr(cmask, C.c_uint8), C.byref(ms)), "osfm_abspose_images_pixels")
+    return _abspose_results(res, n_images), rmask[: len(xy)].astype(bool), cmask[: len(xy)].astype(bool), ms.value
+
+
+def _invert_model(lo_model: np.ndarray) -> np.ndarray:
+    Rt = lo_model.copy()  # multiview.py:487-491
+    R, t = Rt[:3, :3].copy(), Rt[:, 3].copy()
+    Rt[:3, :3] = R.T
+    Rt[:, 3] = -R.T.dot(t)
+    return Rt
+
+
+def absolute_pose_ransac(bs: np.ndarray, Xs: np.ndarray, threshold: float, iterations: int, probability: float, ctx=None) -> np.ndarray:
+    """``multiview.absolute_pose_ransac`` (``multiview.py:468-491``): the inverted lo_model, [R^T | -R^T t]."""
+    # only the iterations are passed on (multiview.py:475-476 sets nothing else), so the probability is the default 0.99 whatever
+    # the caller gives (resect passes 0.999)
+    res, _, _, _ = abspose_images(bs, Xs, [0, len(np.asarray(bs).reshape(-1, 3))], threshold, iterations=iterations, probability=0.99,
+                                  inlier_chord=0.0, ctx=ctx)
+    return _invert_model(res[0]["lo_model"])
+
+
+def reconstructed_points_for_images(tracks_manager, reconstruction, images: Iterable[str]) -> List[Tuple[str, int]]:
+    """Number of reconstructed points visible on each image that is not in the reconstruction (``reconstruction.py:677-692``), sorted by
+    decreasing count (a stable sort, the images in the order given)."""
+    points = reconstruction.points
+    res = {im: sum(1 for track in tracks_manager.get_shot_observations(im) if track in points)
+           for im in images if im not in reconstruction.shots}
+    return sorted(res.items(), key=lambda x: -x[1])
+
+
+def _rig_assignments_per_image(rig_assignments) -> Dict[str, Tuple[str, str, List[str]]]:
+    """``rig.rig_assignments_per_image``: image -> (instance id, rig camera id, the instance's images)"""
+    per_image = {}
+    for instance_id, instance in rig_assignments.items():
+        instance_shots = [s[0] for s in instance]
+        for shot_id, rig_camera_id in instance:
+            per_image[shot_id] = (f"{instance_id}", rig_camera_id, instance_shots)
+    return per_image
+
+
+def _resect_rows(data, tracks_manager, reconstruction, shot_id: str):
+    """the rows of resect's problem: (camera, normalised image points, point coordinates, track ids) of the image's reconstructed tracks"""
+    camera = reconstruction.cameras[data.load_exif(shot_id)["camera"]]
+    xy, Xs, ids = [], [], []
+    for track, obs in tracks_manager.get_shot_observations(shot_id).items():
+        if track in reconstruction.points:
+            xy.append(obs.point)
+            Xs.append(reconstruction.points[track].coordinates)
+            ids.append(track)
+    return camera, np.array(xy, np.float64).reshape(-1, 2), np.array(Xs, np.float64).reshape(-1, 3), ids
+
+
+def _add_shot(data, reconstruction, rig_assignments, shot_id: str, pose, metadata_for: Optional[Callable]) -> Set[str]:
+    """``add_shot`` (``reconstruction.py:247-285``); the shots' metadata comes from ``metadata_for(data, shot_id)`` when given"""
+    from .geometry_types import Pose, RigInstance
+
+    if shot_id not in rig_assignments:
+        shot = reconstruction.create_shot(shot_id, data.load_exif(shot_id)["camera"], pose)
+        if metadata_for is not None:
+            shot.metadata = metadata_for(data, shot_id)
+        return {shot_id}
+    instance_id, _, instance_shots = rig_assignments[shot_id]
+    rig_instance = reconstruction.add_rig_instance(RigInstance(instance_id))
+    for shot in instance_shots:
+        _, rig_camera_id, _ = rig_assignments[shot]
+        created = reconstruction.create_shot(shot, data.load_exif(shot)["camera"], Pose(), rig_camera_id, instance_id)
+        if metadata_for is not None:
+            created.metadata = metadata_for(data, shot)
+    rig_instance.update_instance_pose_with_shot(shot_id, pose)
+    return set(instance_shots)
+
+
+def _resect_finish(data, tracks_manager, reconstruction, rig_assignments, shot_id: str, ids: List[str], lo_model: np.ndarray,
+                   inliers: np.ndarray, min_inliers: int, metadata_for: Optional[Callable], ctx) -> Tuple[bool, Set[str], Dict[str, Any]]:
+    """resect after the estimator (``reconstruction.py:734-762``): the report, and on success the shot(s) and the inlier observations"""
+    from .geometry_types import Pose
+
+    ninliers = int(inliers.sum())
+    report: Dict[str, Any] = {"num_common_points": len(ids), "num_inliers": ninliers}
+    if ninliers < min_inliers:
+        return False, set(), report
+    T = _invert_model(lo_model)
+    R = T[:, :3].T
+    t = -R.dot(T[:, 3])
+    assert shot_id not in reconstruction.shots
+    pose = Pose(translation=t)  # pygeometry.Pose(R, t)
+    pose.set_rotation_matrix(R)
+    new_shots = _add_shot(data, reconstruction, rig_assignments, shot_id, pose, metadata_for)
+    if shot_id in rig_assignments:
+        triangulate_shot_features(tracks_manager, reconstruction, new_shots, data.config, ctx=ctx)
+    for i in np.flatnonzero(inliers):
+        reconstruction.add_observation(shot_id, ids[i], tracks_manager.get_observation(shot_id, ids[i]))
+    report["shots"] = list(new_shots)
+    return True, new_shots, report
+
+
+def _resect_batch(data, tracks_manager, reconstruction, shot_ids: Sequence[str], threshold: float, ctx):
+    """the estimator for several images against the reconstruction as it stands: per image (ids, lo_model or None below 5 rows, inlier mask)"""
+    rows = [_resect_rows(data, tracks_manager, reconstruction, s) for s in shot_ids]
+    solved = [k for k, r in enumerate(rows) if len(r[3]) >= 5]
+    out: List[Tuple[List[str], Optional[np.ndarray], Optional[np.ndarray]]] = [(r[3], None, None) for r in rows]
+    if not solved:
+        return out
+    cam_index: Dict[str, int] = {}
+    models: List[int] = []
+    params: List[np.ndarray] = []
+    image_cam = []
+    for k in solved:
+        cam = rows[k][0]
+        if cam.id not in cam_index:
+            model, par = camera_parameters(cam)
+            cam_index[cam.id] = len(models)
+            models.append(model)
+            params.append(par)
+        image_cam.append(cam_index[cam.id])
+    off = np.r_[0, np.cumsum([len(rows[k][3]) for k in solved])].astype(np.int64)
+    # absolute_pose_ransac(bs, Xs, threshold, 1000, 0.999): the 0.999 is not passed on (multiview.py:475-476 sets only the iterations),
+    # so the probability is the default 0.99
+    res, _, cmask, _ = abspose_images_pixels(np.concatenate([rows[k][1] for k in solved]), np.concatenate([rows[k][2] for k in solved]), off,
+                                             np.array(image_cam, np.int32), np.array(models, np.int32),
+                                             np.array(params, np.float64).reshape(-1, 16), threshold, iterations=1000, probability=0.99,
+                                             inlier_chord=threshold, ctx=ctx)
+    for j, k in enumerate(solved):
+        out[k] = (rows[k][3], res[j]["lo_model"], cmask[off[j]: off[j + 1]])
+    return out
+
+
+def resect(data, tracks_manager, reconstruction, shot_id: str, threshold: float, min_inliers: int, ctx=None,
+           metadata_for: Optional[Callable] = None) -> Tuple[bool, Set[str], Dict[str, Any]]:
+    """Try resecting and adding a shot to the reconstruction (``reconstruction.py:695-762``): same arguments, reports and map updates.
+    The bearings, the LO-RANSAC and the inlier test run on the device.  ``metadata_for(data, shot_id)`` (optional) supplies the shots'
+    metadata (the reference reads EXIF and the control plane there, ``helpers.get_image_metadata``); without it they keep the default."""
+    rig_assignments = _rig_assignments_per_image(data.load_rig_assignments())
+    ids, lo_model, inliers = _resect_batch(data, tracks_manager, reconstruction, [shot_id], threshold, ctx)[0]
+    if lo_model is None:
+        return False, set(), {"num_common_points": len(ids)}
+    return _resect_finish(data, tracks_manager, reconstruction, rig_assignments, shot_id, ids, lo_model, inliers, min_inliers, metadata_for, ctx)
+
+
+def resect_candidates(data, tracks_manager, reconstruction, candidates: Sequence[Tuple[str, int]], threshold: float, min_inliers: int,
+                      max_batch: int = 8, ctx=None, metadata_for: Optional[Callable] = None) -> Dict[str, Any]:
+    """The ``for image, _ in candidates`` loop of ``grow_reconstruction`` (``reconstruction.py:1525-1575``) up to its first success, as
+    batched calls: the reconstruction does not change while candidates fail and every estimate seeds its own generator, so up to
+    ``max_batch`` candidates are solved at once and the first that succeeds is taken -- the loop's result exactly.
+    ``candidates``: what ``reconstructed_points_for_images`` returns.
+    -> {"image": the image added or None, "new_shots": set, "report": its report or None, "failed": [(image, report), ...] of the
+    candidates tried before it, in order}."""
+    if max_batch < 1:
+        raise ValueError("resect_candidates: max_batch must be at least 1")
+    rig_assignments = _rig_assignments_per_image(data.load_rig_assignments())
+    images = [c[0] for c in candidates]
+    failed: List[Tuple[str, Dict[str, Any]]] = []
+    for start in range(0, len(images), max_batch):
+        batch = images[start: start + max_batch]
+        for image, (ids, lo_model, inliers) in zip(batch, _resect_batch(data, tracks_manager, reconstruction, batch, threshold, ctx)):
+            if lo_model is None:
+                ok, new_shots, report = False, set(), {"num_common_points": len(ids)}
+            else:
+                ok, new_shots, report = _resect_finish(data, tracks_manager, reconstruction, rig_assignments, image, ids, lo_model, inliers,
+                                                       min_inliers, metadata_for, ctx)
+            if ok:
+                return {"image": image, "new_shots": new_shots, "report": report, "failed": failed}
+            failed.append((image, report))
+    return {"image": None, "new_shots": set(), "report": None, "failed": failed}

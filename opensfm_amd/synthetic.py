@@ -555,3 +555,94 @@ def make_general_ba_scene(n_shots: int, n_points: int, track_len: int = 10, mode
         alt[pick[::2]] = 0
         prob.update({"point_prior": pp, "point_prior_sigma": ps, "point_prior_has_altitude": alt})
     return prob
+
+
+# ------------------------------------------------------------------------------------------------
+# a map to resect into (reconstruction.resect / resect_candidates)
+# ------------------------------------------------------------------------------------------------
+class ResectionData:
+    """what ``resect`` reads from a DataSet: the config, every image's camera, the rig assignments"""
+
+    def __init__(self, cameras, image_camera, rig_assignments):
+        self.config = {"triangulation_threshold": 0.006, "triangulation_min_ray_angle": 1.0, "triangulation_min_depth": 0.001,
+                       "triangulation_refinement_iterations": 10, "triangulation_type": "FULL", "resection_threshold": 0.004,
+                       "resection_min_inliers": 10}
+        self._cameras, self._image_camera, self._rig_assignments = cameras, image_camera, rig_assignments
+
+    def load_camera_models(self):
+        return self._cameras
+
+    def load_exif(self, image):
+        return {"camera": self._image_camera[image]}
+
+    def load_rig_assignments(self):
+        return self._rig_assignments
+
+
+def make_resection_scene(n_shots: int = 12, n_points: int = 600, seed: int = 5, noise: float = 1e-4):
+    """A reconstruction of `n_shots` perspective shots and `n_points` points at their true places, its tracks manager, and images held
+    out of it: ``held_few_points`` (4 of its tracks are reconstructed), ``held_few_inliers`` (40 rows, most of them wrong),
+    ``held_ok`` (300 rows, a fifth of them wrong), and ``rig_a`` / ``rig_b``, the two shots of rig instance ``inst0`` (``rig_b`` sits on a
+    rig camera half a unit to the side), which also share 80 tracks the reconstruction does not hold.
+    -> (data, tracks_manager, reconstruction, {held-out image: true world-to-camera (R, t)})"""
+    from .geometry_types import Camera, Observation, Pose, Reconstruction, RigCamera, TracksManager
+
+    rng = np.random.default_rng(seed)
+    cam = Camera.create_perspective(0.9, 0.0, 0.0)
+    cam.id = "cam"
+    rec = Reconstruction()
+    rec.add_camera(cam)
+    tm = TracksManager()
+    extra = 130
+    X = np.c_[rng.uniform(-4, 4, n_points + extra), rng.uniform(-3, 3, n_points + extra), rng.uniform(6, 12, n_points + extra)]
+    tracks = ["t%04d" % i for i in range(n_points + extra)]
+
+    def random_pose():
+        R = _rodrigues(rng.normal(0, 0.08, 3))
+        o = np.array([rng.uniform(-3, 3), rng.uniform(-1, 1), rng.uniform(-1, 1)])
+        return R, -R @ o
+
+    def observe(image, R, t, ids, wrong=0.0):
+        Xc = X[ids] @ R.T + t
+        xy = cam.focal * Xc[:, :2] / Xc[:, 2:3] + rng.normal(0, noise, (len(ids), 2))
+        bad = rng.random(len(ids)) < wrong
+        xy[bad] = rng.uniform(-0.5, 0.5, (int(bad.sum()), 2))
+        for i, p in zip(ids, xy):
+            tm.add_observation(image, tracks[i], Observation(p[0], p[1], 0.004))
+
+    image_camera = {}
+    for s in range(n_shots):
+        image = "im%02d" % s
+        image_camera[image] = cam.id
+        R, t = random_pose()
+        pose = Pose(translation=t)
+        pose.set_rotation_matrix(R)
+        rec.create_shot(image, cam.id, pose)
+        observe(image, R, t, np.flatnonzero(rng.random(n_points) < 0.6))
+    for i in range(n_points):
+        rec.create_point(tracks[i], X[i])
+    for image in list(rec.shots):
+        for track, obs in tm.get_shot_observations(image).items():
+            rec.add_observation(image, track, obs)
+    truth = {}
+    new = np.arange(n_points, n_points + extra)
+    for image, ids, wrong in (("held_few_points", np.r_[rng.choice(n_points, 4, replace=False), new[80:]], 0.0),
+                              ("held_few_inliers", rng.choice(n_points, 40, replace=False), 0.85),
+                              ("held_ok", rng.choice(n_points, 300, replace=False), 0.2)):
+        image_camera[image] = cam.id
+        truth[image] = random_pose()
+        observe(image, *truth[image], ids, wrong)
+    # a rig instance of two shots: pose(shot) = pose(rig camera) o pose(instance)
+    Ri, ti = random_pose()
+    Rb, tb = _rodrigues(np.array([0.0, 0.05, 0.0])), np.array([-0.5, 0.0, 0.0])
+    rc_b = Pose(translation=tb)
+    rc_b.set_rotation_matrix(Rb)
+    rec.add_rig_camera(RigCamera("rc_a"))
+    rec.add_rig_camera(RigCamera("rc_b", rc_b))
+    truth["rig_a"] = (Ri, ti)
+    truth["rig_b"] = (Rb @ Ri, Rb @ ti + tb)
+    for image in ("rig_a", "rig_b"):
+        image_camera[image] = cam.id
+        observe(image, *truth[image], np.r_[rng.choice(n_points, 200, replace=False), new[:80]], 0.1)
+    data = ResectionData({cam.id: cam}, image_camera, {"inst0": [("rig_a", "rc_a"), ("rig_b", "rc_b")]})
+    return data, tm, rec, truth
