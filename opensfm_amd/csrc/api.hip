@@ -55,6 +55,7 @@ extern "C" void osfm_ctx_destroy(osfm_ctx *c) {
   if (c->h_pinned) (void)hipHostFree(c->h_pinned);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
   if (c->d_hahog_tables) (void)hipFree(c->d_hahog_tables);
+  if (c->d_match_tickets) (void)hipFree(c->d_match_tickets);
   for (int i = 0; i < 2; ++i)
     if (c->ev_side[i]) (void)hipEventDestroy(c->ev_side[i]);
   for (int i = 0; i < 2; ++i)

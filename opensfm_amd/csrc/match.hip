@@ -3,8 +3,8 @@
 // Replaces, per image pair, the cv2 calls under opensfm/matching.py:723-777
 // (match_brute_force / match_brute_force_symmetric): an n1 x n2 x 128 distance computation, the
 // two nearest neighbours of every feature in BOTH directions, the ratio test and the set
-// intersection -- in ONE kernel, one workgroup per pair.  The n1 x n2 distance matrix never
-// leaves the register file.
+// intersection -- in ONE kernel, one workgroup at a time per pair (the fused kernels: a resident grid of
+// workgroups that draw their pairs by ticket).  The n1 x n2 distance matrix never leaves the register file.
 //
 // Arithmetic (exact, integer): descriptors are integer-valued in [0,255] (features.py:526-534);
 // stored as int8 a' = a - 128.  d^2(a,b) = |a'|^2 + |b'|^2 - 2 a'.b'  with a'.b' from
@@ -19,6 +19,7 @@
 // (Earlier generations -- exact top-2 in both directions 0.16, both directions per pass 0.24, one direction per pass with packed
 // keys 0.39 of the int8 peak, profiles/r01_*, r02_bench_mid.json -- were removed; the exact VALU kernel below remains as the
 // on-GPU cross-check.)
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -29,13 +30,13 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 #ifdef OSFM_DBG_PHASES
 // instrumented builds only (tools/match_phases.py): 100 MHz ticks of workgroup thread 0, summed over the workgroups
-__device__ unsigned long long g_phase[16];
+__device__ unsigned long long g_phase[22];
 #define OSFM_TICK(var) const unsigned long long var = wall_clock64();
-#define OSFM_PHASE(i, t0, t1) if (tid == 0) atomicAdd(&g_phase[i], (t1) - (t0));
+#define OSFM_PHASE(i, t0, t1) if (threadIdx.x == 0) atomicAdd(&g_phase[i], (t1) - (t0));
 extern "C" int osfm_dbg_phases(unsigned long long *out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(g_phase)) != hipSuccess) return 1;
   if (reset) {
-    unsigned long long z[16] = {};
+    unsigned long long z[22] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)) != hipSuccess) return 1;
   }
   return 0;
@@ -95,7 +96,11 @@ struct MatchArgs {
   // register allocation tests/test_kernel_budgets.py pins) does not move
   const uint32_t *bin;  // binary store: 16 dwords per row (tile * 32 + r)
   const float *seg;     // segmentation column (129th descriptor dimension, label x 35) per row, or null
+  // fused kernels only (behind the rest for the same reason): the ticket counters of the resident grid, one per XCD range of the
+  // pair list, kTicketStride ints apart (a 128-byte line each); zeroed on the stream ahead of every launch
+  int32_t *tickets;
 };
+constexpr int kTicketStride = 32;
 
 // ---------------------------------------------------------------------------------------------
 // Shared tail: ratio test on the column side, mutual check, ordered compaction.
@@ -257,11 +262,19 @@ struct QueryPassShared {
 // query of the pass got a target (workgroup-uniform: the OR goes through *hit_word, an LDS word that is zero on entry, across the
 // pass's closing barrier.  Not __syncthreads_or: the library's workgroup reduction brings static LDS of its own, and the kernel
 // already asks for the whole 160 KiB as dynamic LDS).
-template <bool GATHER, bool FQ>
+// hooks: what the caller wants done under the pass, where a round trip to memory costs the pass nothing (the fused kernel fetches its
+// next pair there): cold_issue() between the issue of the pass's first (cold) loads and the wait for them, cold_done() after that
+// wait, chunk(c) behind the barrier that opens chunk c and ahead of every load of its sweep.
+template <bool GATHER, bool FQ, class Hooks>
 __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_t *tilesQ, const int32_t *normQ, int nQ, int nslots,
                                           const unsigned short *qsel, const int8_t *tilesT, const int32_t *normT, const int32_t *hnegT,
                                           int nT, const int8_t *tiles_pad, const int32_t *hneg_pad, unsigned short *out, double ratio,
-                                          int tid, const float *descQ, const float *descT, double eps, int *hit_word, int &any_hit) {
+                                          int tid, const float *descQ, const float *descT, double eps, int *hit_word, int &any_hit,
+                                          Hooks &&hooks) {
+  // the pass runs inside the fused kernel's loop over pairs: what it derives from the thread index is made per call, so that nothing
+  // of it is hoisted out of that loop and kept in vector registers through the other pass's sweep
+  asm volatile("" : "+v"(tid));
+  asm volatile("" : "+s"(ratio));  // (likewise what the float store derives from the ratio in double precision)
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tT = (nT + 31) >> 5;
@@ -465,7 +478,9 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
   v4i afA[kRT][4], afB[kRT][4];
   load_targets(0, afA, 0);
   int myna_next = load_norm(0);
+  hooks.cold_issue();
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): chunk 0, the first targets and their seeds
+  hooks.cold_done();
   read_seeds(0);
   int sidx = 0;  // global step counter: the seeds of step s are staged in slot s & 1
 
@@ -505,6 +520,7 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
       ++sidx;
     };
     OSFM_TICK(tk0)
+    hooks.chunk(c);
     if (c + 1 < nchunks) dma_chunk(c + 1);  // its buffer was released by the merge of chunk c - 1; older than every load of the sweep
     int rb = 0;
     for (; rb + 1 < nrb; rb += 2) {
@@ -722,6 +738,118 @@ __device__ __forceinline__ int query_pass(const QueryPassShared &sh, const int8_
   return flag;
 }
 
+// The grid is resident: min(n_pairs, 2 x CUs) workgroups, each of which draws pairs by ticket until the list is used up.  Blocks are
+// dealt round-robin to the 8 XCDs, and the blocks with the same (blockIdx & 7) share one ticket counter and one contiguous eighth of
+// the pair list, so that the pairs in flight on one L2 share their first image (what xcd_remap gave the one-workgroup-per-pair
+// grid); where a block really runs decides locality only.  A block whose own eighth is used up goes on with the eighths behind it
+// (the XCDs do not finish together; without that the slots of the fast ones idle through the tail of the launch).  The NEXT pair is
+// drawn, and its header (image indices, counts, tile offsets) loaded, under pass A of the current pair; it reaches the waves through
+// hdr[] in LDS:
+//   hdr[0] pair index or -1 (the list is used up), hdr[1..6] img1, img2, n1, n2, tile offsets of img1 and img2 (tiles: < 2^31,
+//   osfm_launch_match checks), hdr[7] whether hdr[3..6] are there (or on their way), hdr[8] how many eighths this block has seen empty.
+struct PairRange {
+  long first;
+  int len;
+};
+__device__ __forceinline__ PairRange pair_range(long n_pairs, int x) {  // the ranges of xcd_remap
+  const long q = n_pairs >> 3, r = n_pairs & 7;
+  return PairRange{x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q, (int)(q + (x < r ? 1 : 0))};
+}
+// one thread: the next pair of the block, from the eighth it is in or the next one that has pairs left.  have: ticket t is already
+// drawn from the eighth the block is in.
+__device__ __forceinline__ int draw_pair(const MatchArgs &a, int xcd, int *hdr, bool have, int t) {
+  for (int k = hdr[8]; k < 8; ++k) {
+    const int x = (xcd + k) & 7;
+    const PairRange r = pair_range(a.n_pairs, x);
+    if (!have) t = atomicAdd(a.tickets + x * kTicketStride, 1);
+    have = false;
+    if (t < r.len) {
+      hdr[8] = k;
+      return (int)(r.first + t);
+    }
+  }
+  hdr[8] = 8;
+  return -1;
+}
+// the last of the three dependent round trips of a header: counts and tile offsets of the two images
+__device__ __forceinline__ void finish_pair_header(const MatchArgs &a, int *hdr) {
+  const int img1 = hdr[1], img2 = hdr[2];
+  const int n1 = a.counts[img1], n2 = a.counts[img2];
+  const int o1 = (int)a.tile_off[img1], o2 = (int)a.tile_off[img2];
+  hdr[3] = n1;
+  hdr[4] = n2;
+  hdr[5] = o1;
+  hdr[6] = o2;
+  hdr[7] = 1;
+}
+// All of the header at once, by one thread that waits for each of the three round trips: for a workgroup's first pair and behind a
+// pair that is over before it began (an image with fewer than two features).
+__device__ __forceinline__ void fetch_pair_header(const MatchArgs &a, int xcd, int *hdr) {
+  const int p = draw_pair(a, xcd, hdr, false, 0);
+  hdr[0] = p;
+  hdr[7] = 1;
+  if (p >= 0) {
+    const int img1 = a.pairs[2 * (long)p], img2 = a.pairs[2 * (long)p + 1];
+    hdr[1] = img1;
+    hdr[2] = img2;
+    finish_pair_header(a, hdr);
+  }
+}
+// The same under pass A of the current pair, one round trip at a time and none of them waited for: the ticket's atomic goes out with
+// the pass's cold loads and comes back with them; the image indices (behind the barrier that opens chunk 0) and the counts and tile
+// offsets (chunk 1; a pass of one chunk leaves them to the top of the next pair, finish_pair_header) travel global -> LDS by DMA, so
+// that no vector register holds them through a sweep.  Wave 0 issues them; its vmcnt(0) ahead of the next chunk's barrier, or of the
+// pair's last barrier, lands them for everyone.
+struct NextPairFetch {
+  const MatchArgs &a;
+  int xcd;
+  int *hdr;
+  int tid;
+  int t;
+  __device__ __forceinline__ void cold_issue() {
+    if (tid == 0) {
+      const int k = hdr[8];
+      t = k < 8 ? atomicAdd(a.tickets + ((xcd + k) & 7) * kTicketStride, 1) : 0;
+    }
+  }
+  __device__ __forceinline__ void cold_done() {
+    if (tid == 0) {
+      hdr[0] = draw_pair(a, xcd, hdr, hdr[8] < 8, t);  // (draws again only where the eighth has just run out)
+      hdr[7] = 0;
+    }
+  }
+  __device__ __forceinline__ void chunk(int c) {
+    if (c > 1 || __builtin_amdgcn_readfirstlane(tid >> 6) != 0) return;
+    const int pn = __builtin_amdgcn_readfirstlane(hdr[0]);
+    if (pn < 0) return;
+    if (c == 0) {
+      if (tid < 2)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.pairs + 2 * (long)pn + tid),
+                                         (__attribute__((address_space(3))) void *)(hdr + 1), 4, 0, 0);
+    } else if (tid < 4) {
+      const int img = hdr[1 + (tid & 1)];
+      const int32_t *src = tid < 2 ? a.counts + img : (const int32_t *)(a.tile_off + img);  // (little endian: the low word)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                       (__attribute__((address_space(3))) void *)(hdr + 3), 4, 0, 0);
+      if (tid == 0) hdr[7] = 1;
+    }
+  }
+};
+struct NoFetch {
+  __device__ __forceinline__ void cold_issue() {}
+  __device__ __forceinline__ void cold_done() {}
+  __device__ __forceinline__ void chunk(int) {}
+};
+
+// The thread index as a value of its own for one phase of a pair, made from the wave's index (a scalar register) and the lane
+// count: what a phase derives from it (lane, wave, masks, LDS addresses) is then made in that phase, not hoisted out of the loop over
+// pairs and held, or spilled, through both sweeps -- and neither is the thread index itself.
+__device__ __forceinline__ int fresh_tid(int wave) {
+  int t = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
 template <bool FQ>
 __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -729,60 +857,97 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   sh.bbuf = smem;                               // [2][32 KiB]
   sh.hbuf = (int *)(smem + 2 * kChunkBytes4);  // [2][256]
   int *misc = (int *)(smem + 2 * kChunkBytes4) + 2 * kChunkCols4;  // [16]
-  unsigned short *resA = (unsigned short *)(misc + 16);            // [ncap] per feature of image A
+  int *hdr = misc + 16;                                            // [16] header of the next pair (9 used)
+  unsigned short *resA = (unsigned short *)(hdr + 16);             // [ncap] per feature of image A
   unsigned short *resB = resA + a.ncap;                            // [ncap] per feature of image B
   unsigned short *cand = resB + a.ncap;                            // [ncap] candidate list (features of B)
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, w = tid >> 6;
-  const long p = xcd_remap(blockIdx.x, a.n_pairs);
-  const int img1 = a.pairs[2 * p], img2 = a.pairs[2 * p + 1];
-  const int n1 = a.counts[img1], n2 = a.counts[img2];
-  if (n1 < 2 || n2 < 2) {  // matching.py:363-374 / knnMatch returns < 2 neighbours
-    if (tid == 0) {
-      a.out_counts[p] = 0;
-      a.out_flags[p] = 0;
-    }
-    return;
-  }
-  // symmetric: A = second image (rows of the big pass), B = first image (streamed, shared in L2)
-  const bool rows_second = a.symmetric || a.query_second;
-  const int imgA = rows_second ? img2 : img1, imgB = rows_second ? img1 : img2;
-  const int nA = rows_second ? n2 : n1, nB = rows_second ? n1 : n2;
-  const int8_t *tilesA = a.tiles + a.tile_off[imgA] * OSFM_TILE_BYTES;
-  const int8_t *tilesB = a.tiles + a.tile_off[imgB] * OSFM_TILE_BYTES;
-  const int32_t *normA = a.norms + a.tile_off[imgA] * 32;
-  const int32_t *normB = a.norms + a.tile_off[imgB] * 32;
-  const int32_t *hnegA = a.hneg + a.tile_off[imgA] * 32;
-  const int32_t *hnegB = a.hneg + a.tile_off[imgB] * 32;
+  const int xcd = blockIdx.x & 7;  // the eighth of the pair list this block starts in
   const int8_t *tiles_pad = a.tiles + a.pad_tile * OSFM_TILE_BYTES;  // the store's first slack tile: zero descriptors, padding norms
   const int32_t *hneg_pad = a.hneg + a.pad_tile * 32;
-
-  for (int j = tid; j < a.ncap; j += kThreads) {
-    resA[j] = kNone;
-    resB[j] = kNone;
+  OSFM_TICK(tw0)
+#ifdef OSFM_DBG_PHASES
+  unsigned long long t_prev = tw0;  // end of the previous pair's last write (first pair: the workgroup's first instruction)
+#endif
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (threadIdx.x == 0) {
+    hdr[8] = 0;
+    fetch_pair_header(a, xcd, hdr);
   }
+  __syncthreads();
+  for (;;) {
+  const int tid = fresh_tid(wave);  // (for the top of the pair only: every later phase makes its own)
+  const long p = __builtin_amdgcn_readfirstlane(hdr[0]);
+  if (p < 0) break;  // the list is used up
+  if (__builtin_amdgcn_readfirstlane(hdr[7]) == 0) {  // the previous pass A had one chunk only: the counts and offsets are still to be fetched
+    __syncthreads();
+    if (tid == 0) finish_pair_header(a, hdr);
+    __syncthreads();
+  }
+  const int img1 = __builtin_amdgcn_readfirstlane(hdr[1]), img2 = __builtin_amdgcn_readfirstlane(hdr[2]);
+  const int n1 = __builtin_amdgcn_readfirstlane(hdr[3]), n2 = __builtin_amdgcn_readfirstlane(hdr[4]);
+  const long off1 = __builtin_amdgcn_readfirstlane(hdr[5]), off2 = __builtin_amdgcn_readfirstlane(hdr[6]);
   if (tid == 0) {
     misc[8] = 0;
     misc[9] = 0;   // hit word of pass A
     misc[10] = 0;  // hit word of pass B
   }
-  __syncthreads();
+  __syncthreads();  // the header is read (thread 0 may overwrite it), the previous pair's results are no longer looked at
+  if (n1 < 2 || n2 < 2) {  // matching.py:363-374 / knnMatch returns < 2 neighbours
+    if (tid == 0) {
+      a.out_counts[p] = 0;
+      a.out_flags[p] = 0;
+      fetch_pair_header(a, xcd, hdr);
+    }
+    __syncthreads();
+#ifdef OSFM_DBG_PHASES
+    {  // a bucket of its own, so that the next pair's boundary does not take this pair's handling (a header fetched in one go) with it
+      OSFM_TICK(te)
+      OSFM_PHASE(19, t_prev, te)
+      if (threadIdx.x == 0) atomicAdd(&g_phase[20], 1ull);
+      t_prev = te;
+    }
+#endif
+    continue;
+  }
+  // symmetric: A = second image (rows of the big pass), B = first image (streamed, shared in L2)
+  const bool rows_second = a.symmetric || a.query_second;
+  const int imgA = rows_second ? img2 : img1, imgB = rows_second ? img1 : img2;
+  const int nA = rows_second ? n2 : n1, nB = rows_second ? n1 : n2;
+  const long offA = rows_second ? off2 : off1, offB = rows_second ? off1 : off2;
+  const int8_t *tilesA = a.tiles + offA * OSFM_TILE_BYTES;
+  const int8_t *tilesB = a.tiles + offB * OSFM_TILE_BYTES;
+  const int32_t *normA = a.norms + offA * 32;
+  const int32_t *normB = a.norms + offB * 32;
+  const int32_t *hnegA = a.hneg + offA * 32;
+  const int32_t *hnegB = a.hneg + offB * 32;
+  // (no clear of resA: pass A writes every slot of image A, kNone included; resB is cleared where the candidate list needs it)
   // FQ: the float rows of the two images and the quantisation error bound of the pair
   OSFM_TICK(tq0)
-  const float *descA = FQ ? a.descf + a.tile_off[imgA] * (long)(32 * OSFM_DESC_DIM) : nullptr;
-  const float *descB = FQ ? a.descf + a.tile_off[imgB] * (long)(32 * OSFM_DESC_DIM) : nullptr;
+  const float *descA = FQ ? a.descf + offA * (long)(32 * OSFM_DESC_DIM) : nullptr;
+  const float *descB = FQ ? a.descf + offB * (long)(32 * OSFM_DESC_DIM) : nullptr;
   const double eps = FQ ? (double)a.qerr[imgA] + (double)a.qerr[imgB] : 0.0;
   // any: some query of the last pass run got a partner.  Without one the pair is empty (98 % of an exhaustive list): candidate
   // list, pass B and the emission scan are skipped; the count and the flag (which may still ask for the exact re-run) are written
   int any = 0;
-  int flag = query_pass<false, FQ>(sh, tilesA, normA, nA, nA, nullptr, tilesB, normB, hnegB, nB, tiles_pad, hneg_pad, resA, a.ratio, tid,
-                                   descA, descB, eps, misc + 9, any);
+  // integer store: flag = the pair has to be re-run by the exact kernel; float store: the number of queries evaluated in float
+  auto flush_flag = [&](int f) {
+    if (FQ) {
+      if ((fresh_tid(wave) & 63) == 0 && f) atomicAdd(&misc[8], f);
+    } else if (f) {
+      misc[8] = 1;
+    }
+  };
+  int flag = query_pass<false, FQ>(sh, tilesA, normA, nA, nA, nullptr, tilesB, normB, hnegB, nB, tiles_pad, hneg_pad, resA, a.ratio, fresh_tid(wave),
+                                   descA, descB, eps, misc + 9, any, NextPairFetch{a, xcd, hdr, fresh_tid(wave), 0});
   OSFM_TICK(tq1)
   OSFM_PHASE(10, tq0, tq1)  // pass A
   if (a.symmetric && any) {
     // candidates: the features of B that some row of A chose.  resB doubles as the mark array
     // (0 = chosen) until the candidate list is built, in ascending feature order.
+    const int tid = fresh_tid(wave), lane = tid & 63, w = tid >> 6;
+    for (int j = tid; j < nB; j += kThreads) resB[j] = kNone;  // (only here: nothing reads resB in a pair without candidates)
+    __syncthreads();
     for (int q = tid; q < nA; q += kThreads) {
       const int b = resA[q];
       if (b != kNone) resB[b] = 0;
@@ -813,24 +978,22 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
     OSFM_TICK(tq2)
     OSFM_PHASE(11, tq1, tq2)  // candidate list
     // (nK > 0: some resA named a feature of B)
-    flag += query_pass<true, FQ>(sh, tilesB, normB, nB, nK, cand, tilesA, normA, hnegA, nA, tiles_pad, hneg_pad, resB, a.ratio, tid, descB, descA,
-                                 eps, misc + 10, any);
+    flush_flag(flag);  // (not carried through pass B in a vector register)
+    flag = query_pass<true, FQ>(sh, tilesB, normB, nB, nK, cand, tilesA, normA, hnegA, nA, tiles_pad, hneg_pad, resB, a.ratio, fresh_tid(wave), descB, descA,
+                                 eps, misc + 10, any, NoFetch{});
   }
   OSFM_TICK(tq3)
   OSFM_PHASE(12, tq1, tq3)  // candidate list + pass B
-  // integer store: flag = the pair has to be re-run by the exact kernel; float store: the number of queries evaluated in float
-  if (FQ) {
-    if (lane == 0 && flag) atomicAdd(&misc[8], flag);
-  } else if (flag) {
-    misc[8] = 1;
-  }
+  flush_flag(flag);
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next pair's header has landed in LDS (wave 0's DMAs)
   __syncthreads();
-  if (tid == 0) a.out_flags[p] = misc[8];
+  if (fresh_tid(wave) == 0) a.out_flags[p] = misc[8];
   // ---- ordered emission: over the features of the pair's first image, or (query_second) of its second image,
   //      the order in which the reference lists the matches of match_flann (matching.py:697) ----
   if (!any) {
-    if (tid == 0) a.out_counts[p] = 0;
+    if (fresh_tid(wave) == 0) a.out_counts[p] = 0;
   } else {
+    const int tid = fresh_tid(wave), lane = tid & 63, w = tid >> 6;
     const bool qs = !a.symmetric && a.query_second;
     const unsigned short *res1 = a.symmetric ? resB : resA;  // indexed by the emission feature -> its partner
     const unsigned short *res2 = a.symmetric ? resA : nullptr;
@@ -869,7 +1032,16 @@ __global__ void __launch_bounds__(kThreads, 2) match_fused_kernel(MatchArgs a) {
   OSFM_PHASE(13, tq3, tq4)  // emission
   OSFM_PHASE(14, tq0, tq4)
 #ifdef OSFM_DBG_PHASES
-  if (tid == 0) atomicAdd(&g_phase[15], 1ull);
+  if (threadIdx.x == 0) atomicAdd(&g_phase[15], 1ull);
+  OSFM_PHASE(16, t_prev, tq0)  // boundary: from the previous pair's last write to this pair's pass A (ticket, header, pointers)
+  t_prev = tq4;
+#endif
+  }  // pairs
+#ifdef OSFM_DBG_PHASES
+  if (threadIdx.x == 0) {
+    atomicAdd(&g_phase[17], wall_clock64() - tw0);  // the workgroup's whole life
+    atomicAdd(&g_phase[18], 1ull);
+  }
 #endif
 }
 
@@ -1139,7 +1311,7 @@ __global__ void __launch_bounds__(kThreads) match_hamming_kernel(MatchArgs a) {
 
 }  // namespace
 
-size_t osfm_match_lds_bytes(int ncap) { return (size_t)2 * kChunkBytes4 + 2 * kChunkCols4 * 4 + 64 + (size_t)ncap * 6; }
+size_t osfm_match_lds_bytes(int ncap) { return (size_t)2 * kChunkBytes4 + 2 * kChunkCols4 * 4 + 128 + (size_t)ncap * 6; }
 
 static int ensure_kernel_attributes(int device) {
   static OsfmPerDeviceOnce once;
@@ -1181,9 +1353,24 @@ int osfm_launch_match(osfm_ctx *ctx, const osfm_store *store, const int32_t *d_p
   a.out_matches = d_matches;
   a.out_flags = d_flags;
   a.pad_tile = store->tile_off[store->n_images];
+  a.tickets = nullptr;
   OSFM_REQUIRE(a.ncap <= OSFM_MAX_FEATURES, OSFM_E_UNSUPPORTED, "more than %d features in an image", OSFM_MAX_FEATURES);
   OSFM_REQUIRE(n_pairs < (1ll << 31), OSFM_E_INVALID, "too many pairs in one launch");
   OSFM_TRY(ensure_kernel_attributes(ctx->device));
+  // the fused kernels run as a resident grid, two workgroups per CU, that hands the pairs out by ticket
+  const bool fused = !store->is_binary && !store->d_seg && !exact_kernel && (!store->is_float || store->quantised);
+  unsigned resident = 0;
+  if (fused) {
+    OSFM_REQUIRE(a.pad_tile < (1ll << 31), OSFM_E_UNSUPPORTED, "too many tiles in the store");
+    OSFM_REQUIRE(ctx->num_cus > 0, OSFM_E_INVALID, "the context knows no compute units");
+    // One ticket buffer per context, made on first use without a lock: every matcher launch of a context is enqueued by its
+    // caller on ctx->stream (osfm_match_pairs' stream A), so this memset and the kernel that counts in the buffer are ordered
+    // behind the previous launch's.  A second stream launching the fused matcher on the same context would need tickets of its own.
+    if (!ctx->d_match_tickets) OSFM_HIP(hipMalloc(&ctx->d_match_tickets, 8 * kTicketStride * sizeof(int32_t)));
+    OSFM_HIP(hipMemsetAsync(ctx->d_match_tickets, 0, 8 * kTicketStride * sizeof(int32_t), stream));
+    a.tickets = (int32_t *)ctx->d_match_tickets;
+    resident = (unsigned)std::min<int64_t>(n_pairs, 2 * (int64_t)ctx->num_cus);
+  }
   if (store->is_binary) {
     // bit strings: Hamming distance on the VALU, every pair in one launch; nothing is ever flagged for a second run.
     // matcher_type FLANN on bit strings (round 6; cv2's LSH index searched EXACTLY, as the kd-forest is for floats): knnSearch returns int32
@@ -1205,14 +1392,14 @@ int osfm_launch_match(osfm_ctx *ctx, const osfm_store *store, const int32_t *d_p
     // Nothing is ever flagged for a second run: out_flags then counts the queries that went through the float evaluation.
     if (exact_kernel && d_flags != nullptr) return OSFM_OK;  // "re-run the flagged pairs": none
     if (!exact_kernel && store->quantised) {
-      hipLaunchKernelGGL(match_fused_kernel<true>, dim3((unsigned)n_pairs), dim3(kThreads), osfm_match_lds_bytes(a.ncap), stream, a);
+      hipLaunchKernelGGL(match_fused_kernel<true>, dim3(resident), dim3(kThreads), osfm_match_lds_bytes(a.ncap), stream, a);
     } else {
       if (d_flags) OSFM_HIP(hipMemsetAsync(d_flags, 0, (size_t)n_pairs * sizeof(int32_t), stream));
       const size_t lds = (size_t)kFloatTileFloats * sizeof(float) + (size_t)a.ncap * 6 + 64;
       hipLaunchKernelGGL(match_float_kernel, dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, a);
     }
   } else if (!exact_kernel) {
-    hipLaunchKernelGGL(match_fused_kernel<false>, dim3((unsigned)n_pairs), dim3(kThreads), osfm_match_lds_bytes(a.ncap), stream, a);
+    hipLaunchKernelGGL(match_fused_kernel<false>, dim3(resident), dim3(kThreads), osfm_match_lds_bytes(a.ncap), stream, a);
   } else {
     const size_t lds = (size_t)a.ncap * 6 + 64;
     hipLaunchKernelGGL(match_exact_kernel, dim3((unsigned)n_pairs), dim3(kThreads), lds, stream, a, d_flags != nullptr ? 1 : 0);

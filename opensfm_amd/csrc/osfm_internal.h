@@ -119,6 +119,7 @@ struct osfm_ctx {
   void *h_stage = nullptr;      // ba.hip: pinned staging memory of a solve's small uploads (4 MiB), made on first use
   void *d_hahog_tables = nullptr;  // hahog.hip: the orientation mask, the exp table and the descriptor's per-pixel table (constants), made on first use
   std::mutex hahog_mu;             // ... under this lock (the batch's worker threads arrive together)
+  void *d_match_tickets = nullptr;  // match.hip: the resident matcher grid's ticket counters (8 lines of 128 B), made on first use
 };
 
 // Tile = 32 descriptors x 128 int8 in MFMA-operand order (4 KiB):
