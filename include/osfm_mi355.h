@@ -435,10 +435,10 @@ int osfm_relpose_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const 
 
 /* =====================================================================================
  * Rotation-only LO-RANSAC of image pairs (reconstruction.compute_image_pairs): the ranking of candidate initial
- * pairs of `opensfm reconstruct`.  relrot.hip / relrot_core.h: one wavefront per pair (lane 0 draws the next block of samples,
- * one 3-point model per lane, the wavefront scores each model over the pair's correspondences in the reference's order); the
- * same launch computes the rotation-only inlier count and the reconstructability score.  The per-pair walk is pinned bit for
- * bit by a host build of the same header (tests/test_relrot_host.py) against a sequential restatement on std::mt19937 and
+ * pairs of `opensfm reconstruct`.  relrot.hip / relrot_core.h (the walk of Estimate too; its sampler: loransac_walk.h): one wavefront per pair (lane
+ * 0 draws the next block of samples, one 3-point model per lane, the wavefront scores each model over the pair's correspondences
+ * in the reference's order); the same launch computes the rotation-only inlier count and the reconstructability score.  The per-pair
+ * walk is pinned bit for bit by a host build of the same headers (tests/test_relrot_host.py) against a sequential restatement on std::mt19937 and
  * against the reference's robust_estimator.h; the GPU is pinned against that host build (tests/test_gpu_relrot.py).
  *
  * osfm_relrot_pairs   pyrobust.ransac_relative_rotation(b1, b2, threshold, params, RANSAC) for every pair of a batch
@@ -481,11 +481,11 @@ int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, 
 
 /* =====================================================================================
  * Absolute-pose (P3P) LO-RANSAC of candidate images (reconstruction.resect, opensfm/reconstruction.py:695-762): the step of
- * grow_reconstruction that adds an image to the map.  abspose.hip / abspose_core.h: one wavefront per image (lane 0 draws the next
+ * grow_reconstruction that adds an image to the map.  abspose.hip / abspose_core.h, the same walk (loransac_walk.h): one wavefront per image (lane 0 draws the next
  * block of samples, four lanes per sample solve one root of the three-point solver's quartic each, the wavefront scores every model
  * over the image's rows in the reference's order; the Lu-Hager solves of a local optimisation run one per lane); the same launch
  * applies resect's inlier test.  The decision path uses + - * / sqrt only (the quartic's complex square and cube roots included), so
- * the walk is pinned bit for bit by a host build of the same header (tests/test_abspose_host.py) against a sequential restatement
+ * the walk is pinned bit for bit by a host build of the same headers (tests/test_abspose_host.py) against a sequential restatement
  * on std::mt19937 and against the reference's robust_estimator.h; the GPU is pinned against that host build
  * (tests/test_gpu_abspose.py).  What is not pinned: Eigen's and libstdc++'s last bits (abspose_core.h says which).
  *

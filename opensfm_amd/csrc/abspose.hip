@@ -1,17 +1,13 @@
 // abspose.hip -- absolute-pose (P3P) LO-RANSAC for a batch of candidate images on gfx950: the estimator of reconstruction.resect.
 //
-// The numerics and the per-image walk live in abspose_core.h (host + device), the GPU wave policy in gpu_wave.h; this file adds the
-// kernels and the C ABI.  One wavefront per image: lane 0 draws the samples of the next block of iterations, four lanes share a
+// The numerics live in abspose_core.h, the per-image walk in loransac_walk.h (both host + device), the GPU wave policy in gpu_wave.h
+// and the batch driver in lo_batch.h; this file adds the kernels and the C ABI.  One wavefront per image: lane 0 draws the samples of the next block of iterations, four lanes share a
 // sample (one root of its quartic each), all lanes score each model over the image's rows (ballot + popcount, inlier list compacted
 // in order); a local optimisation's Lu-Hager solves run one per lane; the same launch ends with resect's inlier test on chords.
 #include <math.h>
 
-#include <algorithm>
-#include <vector>
-
 #include "abspose_core.h"
-#include "gpu_wave.h"
-#include "osfm_internal.h"
+#include "lo_batch.h"
 
 using namespace osfm_ap;
 using osfm_rp::DevBuf;
@@ -63,72 +59,20 @@ __global__ __launch_bounds__(kWave) void ap_solve_kernel(const double *b, const 
 }
 
 int check_args(const int64_t *offsets, int n_images, const osfm_abspose_params *prm, const char *who) {
-  OSFM_REQUIRE(offsets && prm, OSFM_E_INVALID, "%s: null argument", who);
-  OSFM_REQUIRE(n_images >= 0, OSFM_E_INVALID, "%s: n_images < 0", who);
-  OSFM_REQUIRE(prm->iterations >= 0 && prm->lo_iterations >= 0 && prm->threshold > 0 && prm->probability > 0 && prm->probability < 1,
-               OSFM_E_INVALID, "%s: bad parameters", who);
-  if (n_images == 0) return OSFM_OK;
-  OSFM_REQUIRE(offsets[0] == 0, OSFM_E_INVALID, "%s: offsets[0] must be 0", who);
-  for (int p = 0; p < n_images; p++) {
-    OSFM_REQUIRE(offsets[p + 1] - offsets[p] >= kMinimalSamples, OSFM_E_INVALID,
-                 "%s: image %d has %lld rows (at least 3 are needed to draw a sample)", who, p, (long long)(offsets[p + 1] - offsets[p]));
-    OSFM_REQUIRE(offsets[p + 1] - offsets[p] <= (1 << 24), OSFM_E_INVALID, "%s: image %d is too large", who, p);
-  }
-  return OSFM_OK;
+  return osfm_lo::check_batch_args(offsets, n_images, prm, kMinimalSamples, {"image", "rows"}, who);
 }
 
 // The batch on device-resident bearings and points; results and masks copied to the host.  The caller holds the context lock.
 int run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b, const double *d_X, const int64_t *d_off, const int64_t *offsets, int n_images,
                const osfm_abspose_params *prm, osfm_abspose_result *results, uint8_t *ransac_mask, uint8_t *chord_mask, bool timed_from_ev0,
                double *kernel_ms, const char *who) {
-  const int64_t total = offsets[n_images];
-  RngTable rng;
-  OSFM_TRY(osfm_rng_table(ctx, &rng));
-  std::vector<double> stop;
-  std::vector<int64_t> stop_off;
-  osfm_stop_tables(ctx, offsets, n_images, prm->probability, kMinimalSamples, &stop, &stop_off);
-  bool any_large = false;
-  for (int p = 0; p < n_images && !any_large; p++) any_large = offsets[p + 1] - offsets[p] > kLdsInliers;
-  const size_t sizes[] = {stop.size() * 8, stop_off.size() * 8, any_large ? (size_t)total * 4 : 4, (size_t)n_images * sizeof(AbsposeOut),
-                          ransac_mask ? (size_t)total : 1, chord_mask ? (size_t)total : 1, 16};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  double *d_stop = (double *)(base + offs[0]);
-  int64_t *d_stopoff = (int64_t *)(base + offs[1]);
-  int *d_scratch = (int *)(base + offs[2]);
-  AbsposeOut *d_out = (AbsposeOut *)(base + offs[3]);
-  uint8_t *d_rmask = ransac_mask ? (uint8_t *)(base + offs[4]) : nullptr;
-  uint8_t *d_cmask = chord_mask ? (uint8_t *)(base + offs[5]) : nullptr;
-  int *d_flag = (int *)(base + offs[6]);
-  OSFM_HIP(hipMemcpyAsync(d_stop, stop.data(), stop.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_stopoff, stop_off.data(), stop_off.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemsetAsync(d_flag, 0, 16, st));
-  AbsposeArgs A{d_b, d_X, d_off, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), prm->inlier_chord, (int)prm->iterations, (int)prm->use_lo,
-                (int)prm->lo_iterations, (int)prm->use_iteration_reduction, d_scratch, d_out, d_rmask, d_cmask, d_flag};
-  if (!timed_from_ev0) OSFM_HIP(hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(ap_images_kernel, dim3((unsigned)n_images), dim3(kWave), 0, st, A, n_images);
-  OSFM_HIP(hipGetLastError());
-  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
-  int flag = 0;
-  OSFM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(results, d_out, (size_t)n_images * sizeof(AbsposeOut), hipMemcpyDeviceToHost, st));
-  if (ransac_mask) OSFM_HIP(hipMemcpyAsync(ransac_mask, d_rmask, (size_t)total, hipMemcpyDeviceToHost, st));
-  if (chord_mask) OSFM_HIP(hipMemcpyAsync(chord_mask, d_cmask, (size_t)total, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipStreamSynchronize(st));
-  OSFM_REQUIRE(flag == 0, OSFM_E_UNSUPPORTED, "%s: the tabulated mt19937 stream is too short for this input", who);
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
-  return OSFM_OK;
+  auto launch = [&](const osfm_lo::BatchArgs &B, void *d_out, uint8_t *d_rmask, uint8_t *d_cmask) {
+    const AbsposeArgs A{d_b, d_X, B.offsets, B.stop_bound, B.stop_off, B.rng, B.thr, B.chord, B.iterations, B.use_lo, B.lo_iterations,
+                        B.use_reduction, B.scratch, (AbsposeOut *)d_out, d_rmask, d_cmask, B.overflow};
+    hipLaunchKernelGGL(ap_images_kernel, dim3((unsigned)n_images), dim3(kWave), 0, st, A, n_images);
+  };
+  return osfm_lo::run_batch(ctx, st, d_off, offsets, n_images, prm, kMinimalSamples, results, sizeof(AbsposeOut), ransac_mask,
+                            chord_mask, timed_from_ev0, kernel_ms, who, launch);
 }
 
 }  // namespace

@@ -7,7 +7,8 @@
 // solver of the local optimisation; then the inlier count of resect on bearing chords.
 //
 // Everything is host + device, with the discipline of relrot_core.h: tests/native/abspose_host.cpp compiles this header with g++ and
-// runs the very same per-image walk with loops in place of lanes; abspose.hip runs it with one wavefront per image.  Contraction is
+// runs the very same per-image walk (loransac_walk.h over AbsposeModel) with loops in place of lanes; abspose.hip runs it with one wavefront
+// per image.  Contraction is
 // off, every 3-term sum is evaluated left to right, and the decision path uses only + - * / sqrt (frexp / ldexp are exact), so host
 // and device give the same bits.
 //
@@ -36,20 +37,15 @@
 
 namespace osfm_ap {
 
-using osfm_rp::draw_sample_tab;
-using osfm_rp::kLoSampleMax;
-using osfm_rp::kRngCache;
-using osfm_rp::RngTable;
-using osfm_rp::RngView;
+using osfm_lo::kLdsInliers;
+using osfm_lo::kRngCache;
+using osfm_lo::RngTable;
+using osfm_lo::RngView;
 using osfm_rr::closest_rotation;
-using osfm_rr::lo_sample_size;
 using osfm_rr::rotation_between_points;
 
 constexpr int kMinimalSamples = 3;  // AbsolutePose::MINIMAL_SAMPLES
 constexpr int kMaxModels = 4;       // AbsolutePose::MAX_MODELS
-constexpr int kSlots = 16;          // speculative main iterations per block: four lanes per sample, one per root of the quartic
-constexpr int kLoBatch = 64;        // speculative LO iterations per block: one Lu-Hager solve per lane
-constexpr int kLdsInliers = 4096;   // inlier lists of images up to this size stay in LDS; longer ones use per-row scratch
 constexpr int kNPointsIterations = 100;
 constexpr int kCbrtSteps = 8;       // Newton steps of either cube root: quadratic convergence from a start within 26 % / 15 degrees
 
@@ -458,24 +454,24 @@ OSFM_HD double abspose_chord(const double* T, const double* b, const double* X) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One image, one wavefront (policy W: single / parallel_for / count_if / compact / compact_changed / stage_rng).
+// One image, one wavefront: loransac_walk.h's walk over AbsolutePose, then resect's inlier test.
 // ---------------------------------------------------------------------------------------------------------------
+struct AbsposeModel {  // AbsolutePose on the rows of one image
+  static constexpr int kModelSize = 12, kMinimalSamples = osfm_ap::kMinimalSamples, kMaxModels = osfm_ap::kMaxModels;
+  static constexpr int kSlots = 16;    // speculative main iterations per block: four lanes per sample, one per root of the quartic
+  static constexpr int kLoBatch = 64;  // speculative LO iterations per block: one Lu-Hager solve per lane (up to 100 dependent SVDs:
+                                       // the latency of this walk)
+  const double *b, *X;
+  double thr;
+  OSFM_HD int solve_minimal(const int* idx, int root, double* out) const { return p3p_model_of_root(b, X, idx, root, out); }
+  OSFM_HD void solve_nonminimal(const int* idx, int size, double* out) const { npoints_model(b, X, idx, size, out); }
+  OSFM_HD bool inlier(const double* model, int i) const { return abspose_ransac_inlier(model, b + 3 * i, X + 3 * i, thr); }
+};
+using AbsposeShared = osfm_lo::WalkShared<AbsposeModel>;
+
 struct AbsposeOut {  // mirrors osfm_abspose_result
   double model[12], lo_model[12];
   int32_t score, iterations, num_inliers;
-};
-
-struct AbsposeShared {  // LDS of a walk
-  uint32_t rng[kRngCache];
-  double models[kSlots][kMaxModels][12];
-  int nmodels[kSlots];
-  int sidx[kSlots][kMinimalSamples];
-  int pos_after[kSlots];
-  double lo[kLoBatch][12];
-  int lidx[kLoBatch][kLoSampleMax];
-  int lo_pos_after[kLoBatch];
-  int overflow, changed;
-  int inl[kLdsInliers];
 };
 
 struct AbsposeArgs {
@@ -495,130 +491,41 @@ struct AbsposeArgs {
   int* overflow;              // set when the tabulated stream is too short
 };
 
-// Estimate<RansacScoring, AbsolutePose> for image p.  The samples of the next B iterations are drawn by lane 0 and solved four lanes
-// per sample (one per root), assuming no local optimisation fires in between; when one does, the generator has moved and the remaining
-// samples of the block are dropped.  A local optimisation's samples are drawn in one go too, assuming none of them changes the inlier
-// list, and solved one per lane (a Lu-Hager solve is up to 100 dependent SVDs: the latency of this walk); they are scored in order,
-// and at the first one that changes the list the rest are redrawn from the generator position after it.  The decision sequence is
-// the sequential one.
+// Estimate<RansacScoring, AbsolutePose> for image p, and resect's inlier test on the inverted lo_model
 template <class W>
 OSFM_HD void abspose_image(W& w, AbsposeShared& sh, const AbsposeArgs& A, int p) {
   const int64_t o = A.offsets[p];
   const int n = (int)(A.offsets[p + 1] - o);
   const double *b = A.b + 3 * o, *X = A.X + 3 * o;
   int* inliers = n <= kLdsInliers ? sh.inl : A.scratch + o;
-  const double* stop_bound = A.stop_bound + A.stop_off[p];
-  const double thr = A.thr;
-  auto is_inlier = [&](const double* mdl) { return [=](int i) { return abspose_ransac_inlier(mdl, b + 3 * i, X + 3 * i, thr); }; };
-  int pos = 0, it = 0, best = 0, width = 1, stop = 0, failed = 0;
-  double model[12], lo_model[12];
-  for (int i = 0; i < 12; i++) model[i] = lo_model[i] = 0.0;
-  while (it < A.iterations && !stop && !failed) {
-    int B = width < kSlots ? width : kSlots;
-    if (B > A.iterations - it) B = A.iterations - it;
-    const RngView V = w.stage_rng(A.rng, sh.rng, pos, true);
-    w.single([&]() {
-      int q = pos, ovf = 0;
-      for (int k = 0; k < B; k++) {
-        q = draw_sample_tab(V, q, kMinimalSamples, n, sh.sidx[k], &ovf);
-        sh.pos_after[k] = q;
-      }
-      sh.overflow = ovf;
-    });
-    if (sh.overflow) {
-      failed = 1;
-      break;
-    }
-    w.parallel_for(B * kMaxModels, [&](int j) {
-      const int k = j / kMaxModels, r = j % kMaxModels;
-      const int cnt = p3p_model_of_root(b, X, sh.sidx[k], r, sh.models[k][r]);
-      if (r == 0) sh.nmodels[k] = cnt;
-    });
-    int lo_fired = 0;
-    for (int k = 0; k < B && !stop && !lo_fired && !failed; k++) {
-      pos = sh.pos_after[k];
-      const int nm = sh.nmodels[k];
-      for (int j = 0; j < nm && !stop && !failed; j++) {
-        double mk[12];
-        for (int i = 0; i < 12; i++) mk[i] = sh.models[k][j][i];
-        const int cnt = w.count_if(n, is_inlier(mk));
-        if (cnt >= best) {  // std::max(score, best_score): ties keep the newcomer
-          best = cnt;
-          (void)w.compact(n, is_inlier(mk), inliers);
-          for (int i = 0; i < 12; i++) model[i] = lo_model[i] = mk[i];
-        }
-        if (cnt == best && cnt >= kMinimalSamples && A.use_lo && A.lo_iterations > 0) {
-          lo_fired = 1;
-          int l = 0;
-          while (l < A.lo_iterations && !failed) {
-            const int size = lo_sample_size(best);
-            int nb = A.lo_iterations - l;
-            if (nb > kLoBatch) nb = kLoBatch;
-            const RngView V2 = w.stage_rng(A.rng, sh.rng, pos, true);
-            w.single([&]() {
-              int q = pos, ovf = 0;
-              for (int s = 0; s < nb; s++) {
-                int pick[kLoSampleMax];
-                q = draw_sample_tab(V2, q, size, best, pick, &ovf);
-                for (int i = 0; i < size; i++) sh.lidx[s][i] = inliers[pick[i]];
-                sh.lo_pos_after[s] = q;
-              }
-              sh.overflow = ovf;
-            });
-            if (sh.overflow) {
-              failed = 1;
-              break;
-            }
-            w.parallel_for(nb, [&](int s) { npoints_model(b, X, sh.lidx[s], size, sh.lo[s]); });
-            for (int s = 0; s < nb; s++) {
-              pos = sh.lo_pos_after[s];
-              l++;
-              double lm[12];
-              for (int i = 0; i < 12; i++) lm[i] = sh.lo[s][i];
-              const int c2 = w.count_if(n, is_inlier(lm));
-              if (c2 >= best) {  // lo_score.model = best_score.model: only lo_model changes
-                w.single([&]() { sh.changed = c2 != best; });
-                best = c2;
-                (void)w.compact_changed(n, is_inlier(lm), inliers, &sh.changed);
-                for (int i = 0; i < 12; i++) lo_model[i] = lm[i];
-                if (sh.changed) break;  // the later samples were drawn from the list as it was
-              }
-            }
-          }
-        }
-        if (A.use_reduction) stop = stop_bound[best] < (double)it;
-      }
-      it++;
-    }
-    // new bests come early and in bursts: speculate little right after a local optimisation, more once the blocks run through
-    width = lo_fired ? it / 2 + 2 : 2 * B;
-  }
+  osfm_lo::WalkResult<AbsposeModel> r;
+  osfm_lo::walk(w, sh, AbsposeModel{b, X, A.thr}, A, A.stop_bound + A.stop_off[p], n, inliers, r);
   int ninl = -1;
   double T[12];
-  invert_model(lo_model, T);
+  invert_model(r.lo_model, T);
   const double chord = A.chord;
   auto chord_inlier = [&](int i) { return abspose_chord(T, b + 3 * i, X + 3 * i) < chord; };
-  const bool tail = !failed && chord > 0.0;
+  const bool tail = !r.failed && chord > 0.0;
   if (tail) ninl = w.count_if(n, chord_inlier);
   if (A.ransac_mask) {
     uint8_t* mask = A.ransac_mask + o;
     w.parallel_for(n, [&](int i) { mask[i] = 0; });
-    w.parallel_for(failed ? 0 : best, [&](int i) { mask[inliers[i]] = 1; });
+    w.parallel_for(r.failed ? 0 : r.best, [&](int i) { mask[inliers[i]] = 1; });
   }
   if (A.chord_mask) {
     uint8_t* mask = A.chord_mask + o;
     w.parallel_for(n, [&](int i) { mask[i] = (tail && chord_inlier(i)) ? 1 : 0; });
   }
   w.single([&]() {
-    AbsposeOut& r = A.out[p];
+    AbsposeOut& out = A.out[p];
     for (int i = 0; i < 12; i++) {
-      r.model[i] = model[i];
-      r.lo_model[i] = lo_model[i];
+      out.model[i] = r.model[i];
+      out.lo_model[i] = r.lo_model[i];
     }
-    r.score = best;
-    r.iterations = it;
-    r.num_inliers = ninl;
-    if (failed) *A.overflow = 1;
+    out.score = r.best;
+    out.iterations = r.iterations;
+    out.num_inliers = ninl;
+    if (r.failed) *A.overflow = 1;
   });
 }
 

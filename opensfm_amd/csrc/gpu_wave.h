@@ -1,5 +1,6 @@
-// gpu_wave.h -- the GPU side of the wave policy that relpose_rounds.h and relrot_core.h are written against (one wavefront = one
-// workgroup; the host tests run the same walks with loops in place of lanes), and a scoped device buffer.
+// gpu_wave.h -- the GPU side of the wave policy that the walks of relpose_rounds.h and loransac_walk.h are written against (one
+// wavefront = one workgroup; the host tests run the same walks with tests/native/loop_wave.h's loops in place of lanes), and a scoped
+// device buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 

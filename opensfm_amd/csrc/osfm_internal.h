@@ -34,12 +34,12 @@ inline bool osfm_parse_pool_bytes(const char *s, size_t *out) {
 // hipMalloc for the allocations that do not come from the context's block cache: when the device is out of memory while blocks sit
 // idle in the cache, the cache is dropped (osfm_ctx_trim_pool) and the allocation retried
 hipError_t osfm_malloc_retry(osfm_ctx *ctx, void **p, size_t bytes);
-namespace osfm_rp {
+namespace osfm_lo {
 struct RngTable;
 }
-// relpose.hip, shared by the LO-RANSAC drivers (relpose.hip, relrot.hip); the caller holds the context lock.
+// relpose.hip, shared by the LO-RANSAC drivers (relpose.hip, lo_batch.h); the caller holds the context lock.
 // The context's device copy of the std::mt19937(42) stream, made on first use:
-int osfm_rng_table(osfm_ctx *ctx, osfm_rp::RngTable *out);
+int osfm_rng_table(osfm_ctx *ctx, osfm_lo::RngTable *out);
 // ShouldStop's bound (robust_estimator.h:20-35, exponent minimal_samples) for every best inlier count 0 .. n of every pair: *stop holds one
 // table per distinct pair size, pair p's at *stop + (*stop_off)[p]; the tables are cached on the context
 void osfm_stop_tables(osfm_ctx *ctx, const int64_t *offsets, int n_pairs, double probability, int minimal_samples, std::vector<double> *stop,

@@ -27,76 +27,26 @@
 // recorded per sample, so the sequence of draws the reference would make is reproduced exactly.
 //
 // std::mt19937(42) is the same stream for every pair: its raw outputs are tabulated once (RngTable) and a generator "state" is
-// an index into the table -- nothing to snapshot, rewind or replay.
+// an index into the table -- nothing to snapshot, rewind or replay.  The table and the sampler on it live in loransac_walk.h.
 //
 // All functions are host + device: tests/native/relpose_core_host.cpp runs the very same round logic with loops in place of
 // wavefronts and compares every result bit for bit with the CPU oracle.
 #pragma once
+#include "loransac_walk.h"
 #include "relpose_core.h"
 
 namespace osfm_rp {
 
+using osfm_lo::draw_sample_tab;  // the sampler on the tabulated stream (loransac_walk.h)
+using osfm_lo::kLoSampleMax;
+using osfm_lo::kRngCache;
+using osfm_lo::RngTable;
+using osfm_lo::RngView;
+
 constexpr int kWave = 64;
 constexpr int kMaxModels = 10;   // RelativePose::MAX_MODELS
 constexpr int kMaxSlots = 16;    // speculative main iterations per round, at most
-constexpr int kLoSampleMax = 12; // lo_sample_size_clamp
-
-struct RngTable {
-  const uint32_t* tab;  // raw outputs of std::mt19937(42), in order
-  int size;
-};
-constexpr int kRngCache = 512;  // stream entries a walk stages next to itself before it draws (LDS on the GPU)
 constexpr int kLoIterMax = 64;  // local_optimization_iterations the per-pair scratch is sized for (reference default: 10)
-
-// A window of the stream: entries [cache_pos, cache_pos + cache_n) come from `cache`, everything else from the table
-struct RngView {
-  RngTable T;
-  const uint32_t* cache;
-  int cache_pos, cache_n;
-  OSFM_HD uint32_t get(int i) const {
-    const unsigned k = (unsigned)(i - cache_pos);
-    return k < (unsigned)cache_n ? cache[k] : T.tab[i];
-  }
-};
-
-// RandomSamplesGenerator::GenerateOneSample (robust/random_sampler.h:27-37) on the tabulated stream: `size` distinct indices in
-// [0, n) with std::uniform_int_distribution as libstdc++ >= 11 draws it (Lemire's multiply-shift with rejection).  Returns the
-// stream position after the sample; *overflow is set when the table is too short (the caller then reports it).
-OSFM_HD int draw_sample_tab(const RngView& V, int pos, int size, int n, int* idx, int* overflow) {
-  for (int i = 0; i < size; i++) {
-    int dup;
-    do {
-      const uint32_t range = (uint32_t)n;
-      if (pos >= V.T.size) {
-        *overflow = 1;
-        for (int q = i; q < size; q++) idx[q] = q < n ? q : 0;
-        return pos;
-      }
-      uint64_t product = (uint64_t)V.get(pos++) * (uint64_t)range;
-      uint32_t low = (uint32_t)product;
-      if (low < range) {
-        const uint32_t threshold = (0u - range) % range;
-        while (low < threshold) {
-          if (pos >= V.T.size) {
-            *overflow = 1;
-            for (int q = i; q < size; q++) idx[q] = q < n ? q : 0;
-            return pos;
-          }
-          product = (uint64_t)V.get(pos++) * (uint64_t)range;
-          low = (uint32_t)product;
-        }
-      }
-      idx[i] = (int)(uint32_t)(product >> 32);
-      dup = 0;
-      for (int j = 0; j < i; j++) dup |= idx[j] == idx[i];
-    } while (dup);
-  }
-  return pos;
-}
-OSFM_HD int draw_sample_tab(const RngTable& T, int pos, int size, int n, int* idx, int* overflow) {
-  const RngView V{T, nullptr, 0, 0};
-  return draw_sample_tab(V, pos, size, n, idx, overflow);
-}
 
 // per-pair scratch of a walk (LDS on the GPU)
 struct WalkShared {

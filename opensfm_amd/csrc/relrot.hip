@@ -1,17 +1,12 @@
 // relrot.hip -- rotation-only LO-RANSAC for a batch of image pairs on gfx950: the ranking of reconstruction.compute_image_pairs.
 //
-// The numerics and the per-pair walk live in relrot_core.h (host + device), the GPU wave policy in gpu_wave.h; this file adds the
-// kernels and the C ABI.  One wavefront per pair: lane 0 draws the samples of the next block of iterations, every lane solves one 3-point model,
+// The numerics and the per-pair walk live in relrot_core.h, the sampler on the tabulated stream in loransac_walk.h (both host + device),
+// the GPU wave policy in gpu_wave.h and the batch driver in lo_batch.h; this file adds the kernels and the C ABI.  One wavefront per pair: lane 0 draws the samples of the next block of iterations, every lane solves one 3-point model,
 // all lanes score each model over the pair's correspondences (ballot + popcount, inlier list compacted in order), and the same
 // launch ends with the rotation-only inlier count and the reconstructability score.
 #include <math.h>
 
-#include <algorithm>
-#include <unordered_map>
-#include <vector>
-
-#include "gpu_wave.h"
-#include "osfm_internal.h"
+#include "lo_batch.h"
 #include "relrot_core.h"
 
 using namespace osfm_rr;
@@ -48,69 +43,19 @@ __global__ __launch_bounds__(256) void rr_bearings_kernel(const double *__restri
 }
 
 int check_args(const int64_t *offsets, int n_pairs, const osfm_relrot_params *prm, const char *who) {
-  OSFM_REQUIRE(offsets && prm, OSFM_E_INVALID, "%s: null argument", who);
-  OSFM_REQUIRE(n_pairs >= 0, OSFM_E_INVALID, "%s: n_pairs < 0", who);
-  OSFM_REQUIRE(prm->iterations >= 0 && prm->lo_iterations >= 0 && prm->threshold > 0 && prm->probability > 0 && prm->probability < 1,
-               OSFM_E_INVALID, "%s: bad parameters", who);
-  if (n_pairs == 0) return OSFM_OK;
-  OSFM_REQUIRE(offsets[0] == 0, OSFM_E_INVALID, "%s: offsets[0] must be 0", who);
-  for (int p = 0; p < n_pairs; p++) {
-    OSFM_REQUIRE(offsets[p + 1] - offsets[p] >= kMinimalSamples, OSFM_E_INVALID,
-                 "%s: pair %d has %lld correspondences (at least 3 are needed to draw a sample)", who, p, (long long)(offsets[p + 1] - offsets[p]));
-    OSFM_REQUIRE(offsets[p + 1] - offsets[p] <= (1 << 24), OSFM_E_INVALID, "%s: pair %d is too large", who, p);
-  }
-  return OSFM_OK;
+  return osfm_lo::check_batch_args(offsets, n_pairs, prm, kMinimalSamples, {"pair", "correspondences"}, who);
 }
 
 // The batch on device-resident bearings; results and mask copied to the host.  The caller holds the context lock.
 int run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *d_b2, const int64_t *d_off, const int64_t *offsets, int n_pairs,
                const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, bool timed_from_ev0, double *kernel_ms) {
-  const int64_t total = offsets[n_pairs];
-  RngTable rng;
-  OSFM_TRY(osfm_rng_table(ctx, &rng));
-  std::vector<double> stop;
-  std::vector<int64_t> stop_off;
-  osfm_stop_tables(ctx, offsets, n_pairs, prm->probability, kMinimalSamples, &stop, &stop_off);
-  bool any_large = false;
-  for (int p = 0; p < n_pairs && !any_large; p++) any_large = offsets[p + 1] - offsets[p] > kLdsInliers;
-  const size_t sizes[] = {stop.size() * 8, stop_off.size() * 8, any_large ? (size_t)total * 4 : 4, (size_t)n_pairs * sizeof(RelrotOut),
-                          mask ? (size_t)total : 1, 16};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  double *d_stop = (double *)(base + offs[0]);
-  int64_t *d_stopoff = (int64_t *)(base + offs[1]);
-  int *d_scratch = (int *)(base + offs[2]);
-  RelrotOut *d_out = (RelrotOut *)(base + offs[3]);
-  uint8_t *d_mask = mask ? (uint8_t *)(base + offs[4]) : nullptr;
-  int *d_flag = (int *)(base + offs[5]);
-  OSFM_HIP(hipMemcpyAsync(d_stop, stop.data(), stop.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_stopoff, stop_off.data(), stop_off.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemsetAsync(d_flag, 0, 16, st));
-  RelrotArgs A{d_b1, d_b2, d_off, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), prm->inlier_chord, (int)prm->iterations, (int)prm->use_lo,
-               (int)prm->lo_iterations, (int)prm->use_iteration_reduction, d_scratch, d_out, d_mask, d_flag};
-  if (!timed_from_ev0) OSFM_HIP(hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(rr_pairs_kernel, dim3((unsigned)n_pairs), dim3(kWave), 0, st, A, n_pairs);
-  OSFM_HIP(hipGetLastError());
-  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
-  int flag = 0;
-  OSFM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(results, d_out, (size_t)n_pairs * sizeof(RelrotOut), hipMemcpyDeviceToHost, st));
-  if (mask) OSFM_HIP(hipMemcpyAsync(mask, d_mask, (size_t)total, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipStreamSynchronize(st));
-  OSFM_REQUIRE(flag == 0, OSFM_E_UNSUPPORTED, "osfm_relrot_pairs: the tabulated mt19937 stream is too short for this input");
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
-  return OSFM_OK;
+  auto launch = [&](const osfm_lo::BatchArgs &B, void *d_out, uint8_t *d_mask, uint8_t *) {
+    const RelrotArgs A{d_b1, d_b2, B.offsets, B.stop_bound, B.stop_off, B.rng, B.thr, B.chord, B.iterations, B.use_lo, B.lo_iterations,
+                       B.use_reduction, B.scratch, (RelrotOut *)d_out, d_mask, B.overflow};
+    hipLaunchKernelGGL(rr_pairs_kernel, dim3((unsigned)n_pairs), dim3(kWave), 0, st, A, n_pairs);
+  };
+  return osfm_lo::run_batch(ctx, st, d_off, offsets, n_pairs, prm, kMinimalSamples, results, sizeof(RelrotOut), mask, nullptr,
+                            timed_from_ev0, kernel_ms, "osfm_relrot_pairs", launch);
 }
 
 }  // namespace

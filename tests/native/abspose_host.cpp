@@ -7,47 +7,12 @@
 #include <cstring>
 #include <limits>
 #include <random>
-#include <unordered_map>
 #include <vector>
 
 #include "../../opensfm_amd/csrc/abspose_core.h"
+#include "loop_wave.h"
 
 using namespace osfm_ap;
-
-namespace {
-struct LoopWave {  // "lanes" are loop iterations; single() runs once
-  template <class F> void single(F f) { f(); }
-  template <class F> void parallel_for(int n, F f) { for (int i = 0; i < n; i++) f(i); }
-  template <class P> int count_if(int n, P p) { int c = 0; for (int i = 0; i < n; i++) c += p(i) ? 1 : 0; return c; }
-  template <class P> int compact(int n, P p, int* out) { int c = 0; for (int i = 0; i < n; i++) if (p(i)) out[c++] = i; return c; }
-  template <class P> int compact_changed(int n, P p, int* out, int* changed) {
-    int c = 0;
-    for (int i = 0; i < n; i++)
-      if (p(i)) {
-        if (out[c] != i) *changed = 1;
-        out[c++] = i;
-      }
-    return c;
-  }
-  // the GPU stages a window of the stream in LDS; here a short one, so that both paths of RngView::get are exercised
-  RngView stage_rng(const RngTable& T, uint32_t* buf, int pos, bool want) {
-    int n = 0;
-    if (want)
-      for (; n < kRngCache / 16 && pos + n < T.size; n++) buf[n] = T.tab[pos + n];
-    return RngView{T, buf, pos, n};
-  }
-};
-
-const std::vector<uint32_t>& rng_table() {  // as the device table (relpose.hip kRngTableSize)
-  static const std::vector<uint32_t> t = [] {
-    std::vector<uint32_t> v((size_t)1 << 21);
-    std::mt19937 g(42);
-    for (auto& x : v) x = (uint32_t)g();
-    return v;
-  }();
-  return t;
-}
-}  // namespace
 
 extern "C" {
 
@@ -86,23 +51,12 @@ double host_abspose_chord(const double* lo_model, const double* b, const double*
 int host_abspose_images(const double* b, const double* X, const int64_t* offsets, int n_images, double threshold, double probability,
                         int iterations, int use_lo, int lo_iterations, int use_reduction, AbsposeOut* out, uint8_t* ransac_mask,
                         uint8_t* chord_mask) {
-  const auto& tab = rng_table();
   std::vector<double> stop;
-  std::vector<int64_t> stop_off((size_t)n_images);
-  std::unordered_map<int, int64_t> of_n;
-  for (int p = 0; p < n_images; p++) {
-    const int n = (int)(offsets[p + 1] - offsets[p]);
-    if (n < kMinimalSamples) return -1;
-    auto it = of_n.find(n);
-    if (it == of_n.end()) {
-      it = of_n.emplace(n, (int64_t)stop.size()).first;
-      for (int c = 0; c <= n; c++) stop.push_back(osfm_rp::max_iterations_for(c, n, probability, kMinimalSamples));
-    }
-    stop_off[(size_t)p] = it->second;
-  }
+  std::vector<int64_t> stop_off;
+  if (!stop_tables(offsets, n_images, probability, kMinimalSamples, &stop, &stop_off)) return -1;
   std::vector<int> scratch((size_t)std::max<int64_t>(offsets[n_images], 1));
   int overflow = 0;
-  AbsposeArgs A{b, X, offsets, stop.data(), stop_off.data(), RngTable{tab.data(), (int)tab.size()}, 1.0 - std::cos(threshold), threshold,
+  AbsposeArgs A{b, X, offsets, stop.data(), stop_off.data(), rng_table<21>(), 1.0 - std::cos(threshold), threshold,
                 iterations, use_lo, lo_iterations, use_reduction, scratch.data(), out, ransac_mask, chord_mask, &overflow};
   LoopWave w;
   std::vector<AbsposeShared> sh(1);  // per call: callers run batches on several threads

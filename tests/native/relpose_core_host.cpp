@@ -11,6 +11,7 @@
 #include <random>
 
 #include "../../opensfm_amd/csrc/relpose_rounds.h"
+#include "loop_wave.h"
 
 using namespace osfm_rp;
 
@@ -20,40 +21,6 @@ extern "C" void host_set_max_width(int b) { g_max_width = b; }
 static long g_eig_problems = 0, g_eig_mismatches = 0;
 extern "C" long host_eig_problems() { return g_eig_problems; }
 extern "C" long host_eig_mismatches() { return g_eig_mismatches; }
-
-struct LoopWave {  // "lanes" are loop iterations; single() runs once
-  template <class F> void single(F f) { f(); }
-  template <class F> void parallel_for(int n, F f) { for (int i = 0; i < n; i++) f(i); }
-  template <class P> int count_if(int n, P p) { int c = 0; for (int i = 0; i < n; i++) c += p(i) ? 1 : 0; return c; }
-  template <class P> int compact(int n, P p, int* out) { int c = 0; for (int i = 0; i < n; i++) if (p(i)) out[c++] = i; return c; }
-  template <class P> int compact_changed(int n, P p, int* out, int* changed) {
-    int c = 0;
-    for (int i = 0; i < n; i++)
-      if (p(i)) {
-        if (out[c] != i) *changed = 1;
-        out[c++] = i;
-      }
-    return c;
-  }
-  int atomic_add(int* p, int v) { const int o = *p; *p += v; return o; }
-  // the GPU stages a window of the stream in LDS; here half a window, so that both paths of RngView::get are exercised
-  RngView stage_rng(const RngTable& T, uint32_t* buf, int pos, bool want) {
-    int n = 0;
-    if (want)
-      for (; n < kRngCache / 16 && pos + n < T.size; n++) buf[n] = T.tab[pos + n];
-    return RngView{T, buf, pos, n};
-  }
-};
-
-static const std::vector<uint32_t>& rng_table() {
-  static std::vector<uint32_t> t;
-  if (t.empty()) {
-    std::mt19937 g(42);
-    t.resize(1 << 20);
-    for (auto& v : t) v = (uint32_t)g();
-  }
-  return t;
-}
 
 // The rounds of relpose_rounds.h over a batch of pairs, with loops in place of kernels.  The solver work spaces use the LDS layout
 // of the GPU kernels (LaneArr with stride 64; the "lane" of a problem is its position in the work list modulo 64).
@@ -107,7 +74,7 @@ struct HostRounds {
     }
     u1.resize((size_t)(total > 0 ? total : 1) * 3);
     u2.resize((size_t)(total > 0 ? total : 1) * 3);
-    R = Rounds{b1, b2, u1.data(), u2.data(), off, n_pairs, stop.data(), stop_off.data(), RngTable{rng_table().data(), (int)rng_table().size()}, 1.0 - cos(thr), iterations, use_lo,
+    R = Rounds{b1, b2, u1.data(), u2.data(), off, n_pairs, stop.data(), stop_off.data(), rng_table<20>(), 1.0 - cos(thr), iterations, use_lo,
                lo_it, min_n, g_max_width, st.data(), sidx.data(), pos_before.data(), pos_after.data(), nmodels.data(), models.data(), lidx.data(),
                lo_pos_after.data(), lo_ok.data(), lo_rt.data(), inliers.data(), s5_at6.data(), s5_basis.data(), s5_ok.data(), s5_E.data(), lo_E.data(), list5.data(), listN.data(), counters.data(),
                s5_wr.data(), s5_nreal.data(), s5_valid.data()};
@@ -208,7 +175,7 @@ int host_rounds_ransac_batch(const double* b1, const double* b2, const int64_t* 
 
 // samples of the tabulated stream: `count` samples of `size` distinct indices below n, drawn one after the other
 void host_draw_samples(int n, int size, int count, int* out) {
-  const RngTable T{rng_table().data(), (int)rng_table().size()};
+  const RngTable T = rng_table<20>();
   int pos = 0, overflow = 0;
   for (int c = 0; c < count; c++) pos = draw_sample_tab(T, pos, size, n, out + (size_t)c * size, &overflow);
 }

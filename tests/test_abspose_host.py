@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "opensfm_amd", "csrc")
 REF = "/root/reference/opensfm"
 OUT = os.path.join(HERE, "native", "_build")
-HEADERS = ("abspose_core.h", "relrot_core.h", "relpose_core.h", "relpose_rounds.h")
+HEADERS = ("abspose_core.h", "relrot_core.h", "loransac_walk.h", "relpose_core.h", "relpose_rounds.h")
 THRESHOLD = 0.004
 
 
@@ -29,7 +29,7 @@ def _p(a, t=C.c_double):
 def _compile(name, src, flags, shared=True):
     os.makedirs(OUT, exist_ok=True)
     target = os.path.join(OUT, name)
-    deps = [src, os.path.join(HERE, "native", "abspose_host.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
+    deps = [src, os.path.join(HERE, "native", "abspose_host.cpp"), os.path.join(HERE, "native", "loop_wave.h")] + [os.path.join(CSRC, h) for h in HEADERS]
     if not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps):
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", *(["-fPIC", "-shared"] if shared else []), *flags,
                                "-o", target, src])

@@ -77,6 +77,24 @@ def test_parameters_without_lo_and_reduction_equal_host(host, batch, gpu_ctx):
     assert np.array_equal(rmask, wrmask) and np.array_equal(cmask, wcmask)
 
 
+def test_lo_longer_than_a_batch_equals_host(host, gpu_ctx):
+    """70 local-optimisation iterations, one more than a batch of 64 Lu-Hager solves holds: a second batch per firing, and batches cut
+    short where a sample changes the inlier list.  Rows around the minimal sample and the wavefront; no all-outliers image (its walk is
+    the long one and takes no other path)."""
+    from opensfm_amd import reconstruction
+
+    rng = np.random.default_rng(21)
+    kinds = [k for k in cases.KINDS if k != "all_outliers"]
+    sizes = [3, 4, 5, 63, 64, 65, 300] * 3
+    b, X, off = cases.pack([cases.make_problem(rng, n, kinds[k % len(kinds)], outliers=rng.uniform(0, 0.6)) for k, n in enumerate(sizes)])
+    got, rmask, cmask, _ = reconstruction.abspose_images(b, X, off, THRESHOLD, iterations=60, lo_iterations=70, ctx=gpu_ctx)
+    want, wrmask, wcmask = host_images(host, b, X, off, THRESHOLD, iterations=60, lo_iterations=70)
+    for p in range(len(want)):
+        _assert_equal(got, want, p)
+    assert np.array_equal(rmask, wrmask) and np.array_equal(cmask, wcmask)
+    assert sum(w.score >= 3 for w in want) >= 15  # a local optimisation fired in most of them
+
+
 def test_pixels_twin_equals_bearings_call(gpu_ctx):
     """abspose_images_pixels == abspose_images fed with pixel_bearing_many's bearings, over four camera models"""
     from opensfm_amd import matching, reconstruction

@@ -21,7 +21,8 @@ def build_host():
     out_dir = os.path.join(HERE, "native", "_build")
     os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "relpose_core_host.so")
-    deps = [src] + [os.path.join(HERE, "..", "opensfm_amd", "csrc", h) for h in ("relpose_core.h", "relpose_rounds.h")]
+    deps = [src, os.path.join(HERE, "native", "loop_wave.h")] + [os.path.join(HERE, "..", "opensfm_amd", "csrc", h)
+                                                                   for h in ("relpose_core.h", "relpose_rounds.h", "loransac_walk.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", "-o", so, src])
     return C.CDLL(so)

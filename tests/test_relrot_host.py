@@ -2,7 +2,8 @@
 lanes (tests/native/relrot_host.cpp): the header's walk against an independent sequential restatement of
 Estimate<RansacScoring, RelativeRotation> on this toolchain's std::mt19937, bit for bit; the SVD of RotationBetweenPoints; and,
 where the reference is mounted, the reference's own robust_estimator.h around the same model numerics and its
-test_outliers_relative_rotation_ransac with pyrobust served by the host build."""
+test_outliers_relative_rotation_ransac with pyrobust served by the host build; and a stand-alone program of the walk under the address
+and undefined-behaviour sanitizers."""
 import ctypes as C
 import os
 import subprocess
@@ -17,19 +18,21 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "opensfm_amd", "csrc")
 REF = "/root/reference/opensfm"
 OUT = os.path.join(HERE, "native", "_build")
+HEADERS = ("relrot_core.h", "loransac_walk.h", "relpose_core.h")
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def _build(name, src, extra=()):
+def _build(name, src, extra=(), shared=True):
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, name)
-    deps = [src] + [os.path.join(CSRC, h) for h in ("relrot_core.h", "relpose_core.h", "relpose_rounds.h")]
+    deps = [src, os.path.join(HERE, "native", "relrot_host.cpp"), os.path.join(HERE, "native", "loop_wave.h")] + [os.path.join(CSRC, h) for h in HEADERS]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-std=c++17", *extra, "-o", so, src])
-    return C.CDLL(so)
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", *(["-fPIC", "-shared"] if shared else []), "-std=c++17", *extra,
+                               "-o", so, src])
+    return C.CDLL(so) if shared else so
 
 
 def build_host():
@@ -376,3 +379,12 @@ def test_reference_outliers_relative_rotation_ransac(host):
         pairs.append((X, None, None, None))
     np.random.seed(7)
     ns["test_outliers_relative_rotation_ransac"](pairs)
+
+
+def test_standalone_walk_under_sanitizers():
+    """a stand-alone program of the walk (its own main, run as a child process) under the address and undefined-behaviour sanitizers"""
+    exe = _build("relrot_main", os.path.join(HERE, "native", "relrot_main.cpp"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                 shared=False)
+    done = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert done.returncode == 0, done.stdout + done.stderr
+    assert "relrot_main: ok" in done.stdout
