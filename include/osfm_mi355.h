@@ -731,6 +731,44 @@ int osfm_triangulate_tracks(osfm_ctx *ctx, const double *shot_pose, const int32_
                             int n_tracks, const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used,
                             double *kernel_ms);
 
+/* =====================================================================================
+ * Robust triangulation of tracks (opensfm/reconstruction.py:922-1030 TrackTriangulator.triangulate_robust, `triangulation_type: ROBUST`),
+ * triangulate.hip + triangulate_robust.h: per-track RANSAC over pairs of observations, every track of the batch in one call.
+ *
+ * Per track of n observations in input order (restated literally, the reference's quirks included): n < 2 -> status 1.  C = n (n - 1) / 2
+ * pairs (i < j) in lexicographic order; up to 11 tries, each consuming one uniform draw u:
+ *   id = (int64)(u * (double)(C - 1))  (the last pair is never drawn unless C == 1); an id an earlier try drew costs the try only;
+ *   TriangulateBearingsMidpoint on the rows (i, j) of rank id alone (the pair test, the midpoint and the two per-row tests of the FULL
+ *   path, with threshold, min_angle_deg, min_depth); invalid ends the try; X = PointRefinement(the two rows, midpoint);
+ *   inliers of X over all rows: |(X - o_k) / |X - o_k| - w_k| < threshold (a chord, strict);
+ *   only if there are more than the best so far: new_X = PointRefinement(inlier rows, X); ls_inliers of new_X over all rows; the best is
+ *   (ls_inliers, new_X) if strictly more than the inliers, else (inliers, X); ratio = |best| / n; stop if ratio == 1, else stop if
+ *   log(1 - 0.99) / log(1 - ratio^2) <= i, i being the FIRST INDEX OF THE SAMPLED PAIR (the reference's loop variable is shadowed).
+ * A best of more than one inlier is the point (status 0) and exactly the best inliers observe it; otherwise status 6.  One divergence,
+ * that of the FULL path: a best point that is not finite is status 5.
+ *   status       n_tracks: 0 triangulated, 1 fewer than 2 observations, 5 not finite, 6 no consensus (no valid sample, or a best of
+ *                fewer than 2 inliers);
+ *   points       n_tracks x 3: NaN unless the status is 0;
+ *   inlier_mask  one byte per observation row: 1 for the best inliers of a track of status 0, else 0;
+ *   n_inliers    n_tracks: the number of those (0 unless the status is 0);
+ *   tries_used   n_tracks: draws consumed (tries made, repeats included; 0 for status 1);  kernel_ms may be NULL.
+ * Randomness: track t owns 11 draws and never depends on another track or on the grid.  `draws` is n_tracks x 11 values in [0, 1) (a
+ * value outside, or not finite: OSFM_E_INVALID, found by the kernel), or NULL: draw k of track t is then, in uint64 arithmetic,
+ *   z = seed + 0x9E3779B97F4A7C15 * (11 t + k + 1);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *   z = z ^ (z >> 31);  u = (double)(z >> 11) * 2^-53
+ * (splitmix64's finaliser).  The distribution is the reference's; the stream is not numpy's global generator and cannot be -- the
+ * number of draws the reference consumes per track depends on the outcome of the tracks before it.
+ * Arguments, errors and the order of sums are those of the FULL calls above: two runs are bit-equal.
+ * ===================================================================================== */
+int osfm_triangulate_bearings_robust(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                                     const osfm_triangulate_params *params, const double *draws, uint64_t seed, double *points, uint8_t *status,
+                                     uint8_t *inlier_mask, int32_t *n_inliers, int32_t *tries_used, double *kernel_ms);
+int osfm_triangulate_tracks_robust(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
+                                   const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy,
+                                   const int64_t *track_offsets, int n_tracks, const osfm_triangulate_params *params, const double *draws,
+                                   uint64_t seed, double *points, uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers,
+                                   int32_t *tries_used, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,19 @@ SIGNATURES = {
          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams), C.POINTER(C.c_double),
          C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double)],
     ),
+    "osfm_triangulate_bearings_robust": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams),
+         C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+         C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    ),
+    "osfm_triangulate_tracks_robust": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int,
+         C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams), C.POINTER(C.c_double),
+         C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(C.c_double)],
+    ),
     "osfm_match_guided": (
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float),

@@ -12,12 +12,19 @@
 // the kWaveObs observations a wavefront's LDS slice holds loads the overhang again.
 // Sums: every lane adds its observations in ascending order, then a butterfly over the group (log2 G xor-shuffles): the order depends
 // on the track's length alone (which kernel, which lane), never on the grid or on timing; no atomics on floating-point values.
+//
+// `triangulation_type: ROBUST` (TrackTriangulator.triangulate_robust, the walk of triangulate_robust.h) runs on the same two shapes:
+// tri_group_robust_kernel and tri_wave_robust_kernel share the row loaders, stage() and the host-side split.  The candidate and best
+// masks belong to the lane that owns the observation: one 32-bit word per lane (bit 16 * which + i / G) -- a register in the group
+// kernel (at most 4 observations per lane), an LDS word per lane in the wavefront kernel (8 staged observations per lane) -- and, for
+// the overhang past kWaveObs, bit `which` of the observation's byte of the output mask, which the same lane alone reads and writes.
 #include <math.h>
 
 #include <vector>
 
 #include "osfm_internal.h"
 #include "triangulate_core.h"
+#include "triangulate_robust.h"
 
 using namespace osfm_tri;
 
@@ -200,6 +207,93 @@ __global__ __launch_bounds__(kWave) void tri_wave_kernel(Rows rows, const int64_
   solve_and_store(trk, prm, t, out);
 }
 
+// ---- ROBUST ----
+// LaneTrack plus the two masks of triangulate_robust.h; Overhang says which kernel: the word in a register or in LDS
+template <int G, bool Overhang, class Rows>
+struct RobustLaneTrack : LaneTrack<G, Overhang, Rows> {
+  uint32_t reg;    // group kernel: this lane's mask word
+  uint32_t *word;  // wavefront kernel: this lane's mask word in LDS
+  uint8_t *bytes;  // wavefront kernel: the track's bytes of the output mask, bit `which` of byte i for i >= cap
+  __device__ __forceinline__ bool bit(int which, int i) const {
+    if (Overhang && i >= this->cap) return (bytes[i] >> which) & 1;
+    return ((Overhang ? *word : reg) >> (16 * which + i / G)) & 1;
+  }
+  __device__ __forceinline__ void set_bit(int which, int i, bool b) {
+    if (Overhang && i >= this->cap) {
+      bytes[i] = (uint8_t)((bytes[i] & ~(1 << which)) | ((b ? 1 : 0) << which));
+      return;
+    }
+    const uint32_t m = 1u << (16 * which + i / G);
+    if (Overhang)
+      *word = b ? (*word | m) : (*word & ~m);
+    else
+      reg = b ? (reg | m) : (reg & ~m);
+  }
+};
+static_assert(kGroupObs / kGroup <= 16 && kWaveObs / kWave <= 16, "a mask has 16 bits per lane");
+
+struct RobustOut {
+  double *points;
+  uint8_t *status, *mask;
+  int32_t *n_inliers, *tries;
+  int *bad;              // set when a row could not be evaluated or a draw lies outside [0, 1)
+  const double *draws;   // n_tracks x 11, or null: robust_draw(seed, t, k)
+  uint64_t seed;
+};
+
+template <class Track>
+__device__ __forceinline__ void solve_and_store_robust(Track &trk, const Params &prm, int64_t t, int64_t row0, const RobustOut &out) {
+  double X[3] = {NAN, NAN, NAN};
+  int n_inliers = 0, tries = 0;
+  const Draws11 draw{out.draws ? out.draws + kRobustTries * t : nullptr, out.seed, t};
+  int status = triangulate_track_robust(trk, prm, draw, X, &n_inliers, &tries);
+  if (status == kBadDraws) {
+    if (trk.lane == 0) atomicOr(out.bad, 1);
+    status = kNoConsensus;
+  }
+  for (int i = trk.first(); i < trk.n; i += trk.stride()) out.mask[row0 + i] = (status == kOk && trk.bit(kBest, i)) ? 1 : 0;
+  if (trk.lane != 0) return;
+  for (int k = 0; k < 3; k++) out.points[3 * t + k] = X[k];
+  out.status[t] = (uint8_t)status;
+  out.n_inliers[t] = n_inliers;
+  out.tries[t] = tries;
+}
+
+template <class Rows>
+__global__ __launch_bounds__(kBlock) void tri_group_robust_kernel(Rows rows, const int64_t *__restrict__ offsets, int n_tracks, Params prm,
+                                                                  RobustOut out) {
+  __shared__ double sh[6 * kGroupsPerBlock * kGroupPitch];
+  const int g = (int)threadIdx.x / kGroup, lane = (int)threadIdx.x % kGroup;
+  const int64_t t = (int64_t)blockIdx.x * kGroupsPerBlock + g;
+  const int64_t row0 = t < n_tracks ? offsets[t] : 0;
+  const int64_t len = t < n_tracks ? offsets[t + 1] - row0 : 0;
+  const bool mine = t < n_tracks && len <= kGroupObs;  // the same on every lane of the group
+  const int n = mine ? (int)len : 0;
+  constexpr int plane = kGroupsPerBlock * kGroupPitch;
+  double *slice = sh + g * kGroupPitch;
+  stage<kGroup>(rows, row0, n, kGroupObs, lane, slice, plane, out.bad);
+  __syncthreads();
+  if (!mine) return;
+  RobustLaneTrack<kGroup, false, Rows> trk{{n, lane, kGroupObs, plane, slice, rows, row0}, 0u, nullptr, nullptr};
+  solve_and_store_robust(trk, prm, t, row0, out);
+}
+
+template <class Rows>
+__global__ __launch_bounds__(kWave) void tri_wave_robust_kernel(Rows rows, const int64_t *__restrict__ offsets,
+                                                                const int32_t *__restrict__ long_tracks, Params prm, RobustOut out) {
+  __shared__ double sh[6 * kWaveObs];
+  __shared__ uint32_t words[kWave];
+  const int lane = (int)threadIdx.x;
+  const int64_t t = long_tracks[blockIdx.x];
+  const int64_t row0 = offsets[t];
+  const int n = (int)(offsets[t + 1] - row0);
+  stage<kWave>(rows, row0, n, kWaveObs, lane, sh, kWaveObs, out.bad);
+  words[lane] = 0u;
+  __syncthreads();
+  RobustLaneTrack<kWave, true, Rows> trk{{n, lane, kWaveObs, kWaveObs, sh, rows, row0}, 0u, words + lane, out.mask + row0};
+  solve_and_store_robust(trk, prm, t, row0, out);
+}
+
 int check_args(const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p, const char *who) {
   OSFM_REQUIRE(p, OSFM_E_INVALID, "%s: null params", who);
   OSFM_REQUIRE(n_tracks >= 0, OSFM_E_INVALID, "%s: n_tracks < 0", who);
@@ -216,14 +310,20 @@ int check_args(const int64_t *offsets, int n_tracks, const osfm_triangulate_para
   return OSFM_OK;
 }
 
+// the tracks of the wavefront kernel
+std::vector<int32_t> split_long(const int64_t *offsets, int n_tracks) {
+  std::vector<int32_t> long_tracks;
+  for (int t = 0; t < n_tracks; t++)
+    if (offsets[t + 1] - offsets[t] > kGroupObs) long_tracks.push_back(t);
+  return long_tracks;
+}
+
 // Both kernels over rows that are on the device already; `uploaded` bytes of the arena hold the caller's inputs.  The caller holds the
 // context lock and has recorded nothing on ev[0] / ev[1].
 template <class Rows>
 int run_device(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p,
                const double *initial, double *points, uint8_t *status, int32_t *iterations_used, double *kernel_ms, const char *who) {
-  std::vector<int32_t> long_tracks;
-  for (int t = 0; t < n_tracks; t++)
-    if (offsets[t + 1] - offsets[t] > kGroupObs) long_tracks.push_back(t);
+  const std::vector<int32_t> long_tracks = split_long(offsets, n_tracks);
   const size_t n_long = long_tracks.size();
   const size_t sizes[] = {((size_t)n_tracks + 1) * 8, n_long * 4, (size_t)n_tracks * 24, (size_t)n_tracks, (size_t)n_tracks * 4, 16,
                           initial ? (size_t)n_tracks * 24 : 0};
@@ -268,6 +368,104 @@ int run_device(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *o
     *kernel_ms = ms;
   }
   OSFM_REQUIRE(bad == 0, OSFM_E_INVALID, "%s: an observation names a shot outside the table, or it or its shot's pose is not finite", who);
+  return OSFM_OK;
+}
+
+struct RobustResults {
+  double *points;
+  uint8_t *status, *inlier_mask;
+  int32_t *n_inliers, *tries_used;
+};
+
+// run_device for the robust kernels: the same split and arena, plus the draws (when given) and the per-observation mask
+template <class Rows>
+int run_device_robust(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p,
+                      const double *draws, uint64_t seed, const RobustResults &res, double *kernel_ms, const char *who) {
+  const std::vector<int32_t> long_tracks = split_long(offsets, n_tracks);
+  const size_t n_long = long_tracks.size(), n_obs = (size_t)offsets[n_tracks];
+  const size_t sizes[] = {((size_t)n_tracks + 1) * 8, n_long * 4, (size_t)n_tracks * 24, (size_t)n_tracks, (size_t)n_tracks * 4, (size_t)n_tracks * 4,
+                          16,                         n_obs,      draws ? (size_t)n_tracks * kRobustTries * 8 : 0};
+  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
+  size_t offs[kBuffers], arena_bytes = 0;
+  for (int i = 0; i < kBuffers; i++) {
+    offs[i] = arena_bytes;
+    arena_bytes += (sizes[i] + 255) / 256 * 256;
+  }
+  OsfmPoolBuf arena;
+  OSFM_HIP(arena.alloc(ctx, arena_bytes));
+  char *base = (char *)arena.p;
+  int64_t *d_off = (int64_t *)(base + offs[0]);
+  int32_t *d_long = (int32_t *)(base + offs[1]);
+  RobustOut out{(double *)(base + offs[2]), (uint8_t *)(base + offs[3]), (uint8_t *)(base + offs[7]), (int32_t *)(base + offs[4]),
+                (int32_t *)(base + offs[5]), (int *)(base + offs[6]), draws ? (const double *)(base + offs[8]) : nullptr, seed};
+  if (draws) OSFM_HIP(hipMemcpyAsync(base + offs[8], draws, sizes[8], hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemcpyAsync(d_off, offsets, sizes[0], hipMemcpyHostToDevice, st));
+  if (n_long) OSFM_HIP(hipMemcpyAsync(d_long, long_tracks.data(), sizes[1], hipMemcpyHostToDevice, st));
+  OSFM_HIP(hipMemsetAsync(out.bad, 0, 16, st));
+  if (n_obs) OSFM_HIP(hipMemsetAsync(out.mask, 0, n_obs, st));
+  const Params prm{p->threshold, p->min_angle_deg * M_PI / 180.0, p->min_depth, (int)p->refinement_iterations};
+  OSFM_HIP(hipEventRecord(ctx->ev[0], st));
+  if (n_long < (size_t)n_tracks) {
+    hipLaunchKernelGGL((tri_group_robust_kernel<Rows>), dim3((unsigned)((n_tracks + kGroupsPerBlock - 1) / kGroupsPerBlock)), dim3(kBlock), 0, st,
+                       rows, d_off, n_tracks, prm, out);
+    OSFM_HIP(hipGetLastError());
+  }
+  if (n_long) {
+    hipLaunchKernelGGL((tri_wave_robust_kernel<Rows>), dim3((unsigned)n_long), dim3(kWave), 0, st, rows, d_off, d_long, prm, out);
+    OSFM_HIP(hipGetLastError());
+  }
+  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
+  int bad = 0;
+  OSFM_HIP(hipMemcpyAsync(&bad, out.bad, 4, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(res.points, out.points, sizes[2], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(res.status, out.status, sizes[3], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(res.n_inliers, out.n_inliers, sizes[4], hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(res.tries_used, out.tries, sizes[5], hipMemcpyDeviceToHost, st));
+  if (n_obs) OSFM_HIP(hipMemcpyAsync(res.inlier_mask, out.mask, n_obs, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipStreamSynchronize(st));
+  if (kernel_ms) {
+    float ms = 0.f;
+    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    *kernel_ms = ms;
+  }
+  OSFM_REQUIRE(bad == 0, OSFM_E_INVALID,
+               "%s: an observation names a shot outside the table, it or its shot's pose is not finite, or a draw lies outside [0, 1)", who);
+  return OSFM_OK;
+}
+
+int check_robust_results(const RobustResults &res, int64_t n_obs, const char *who) {
+  OSFM_REQUIRE(res.points && res.status && res.n_inliers && res.tries_used, OSFM_E_INVALID, "%s: null points / status / n_inliers / tries_used", who);
+  OSFM_REQUIRE(n_obs == 0 || res.inlier_mask, OSFM_E_INVALID, "%s: null inlier_mask", who);
+  return OSFM_OK;
+}
+
+// the tables and rows of a pixel call, checked and on their way to the device (the caller holds the context lock; `in` owns the memory)
+int upload_pixel_rows(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
+                      const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy, int64_t n_obs, OsfmPoolBuf &in,
+                      PixelRows *rows, const char *who) {
+  OSFM_REQUIRE(n_obs == 0 || (shot_pose && shot_camera && cam_model && cam_params && obs_shot && obs_xy && n_shots > 0 && n_cams > 0),
+               OSFM_E_INVALID, "%s: null argument", who);
+  for (int c = 0; c < n_cams; c++)
+    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
+                 c, cam_model[c]);
+  for (int s = 0; s < n_shots; s++)
+    OSFM_REQUIRE(shot_camera[s] >= 0 && shot_camera[s] < n_cams, OSFM_E_INVALID, "%s: shot %d names a camera outside the table", who, s);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t sizes[] = {(size_t)n_shots * 96, (size_t)n_shots * 4, (size_t)n_cams * 4, (size_t)n_cams * 128, (size_t)n_obs * 4, (size_t)n_obs * 16};
+  const void *src[] = {shot_pose, shot_camera, cam_model, cam_params, obs_shot, obs_xy};
+  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
+  size_t offs[kBuffers], arena_bytes = 0;
+  for (int i = 0; i < kBuffers; i++) {
+    offs[i] = arena_bytes;
+    arena_bytes += (sizes[i] + 255) / 256 * 256;
+  }
+  OSFM_HIP(in.alloc(ctx, arena_bytes));
+  char *base = (char *)in.p;
+  for (int i = 0; i < kBuffers; i++)
+    if (sizes[i]) OSFM_HIP(hipMemcpyAsync(base + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st));
+  *rows = PixelRows{(const double *)(base + offs[0]), (const int32_t *)(base + offs[1]), (const int32_t *)(base + offs[2]),
+                    (const double *)(base + offs[3]), (const int32_t *)(base + offs[4]), (const double *)(base + offs[5]), n_shots};
   return OSFM_OK;
 }
 
@@ -318,31 +516,11 @@ extern "C" int osfm_triangulate_tracks(osfm_ctx *ctx, const double *shot_pose, c
   if (n_tracks == 0) return OSFM_OK;
   OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
   const int64_t n_obs = track_offsets[n_tracks];
-  OSFM_REQUIRE(n_obs == 0 || (shot_pose && shot_camera && cam_model && cam_params && obs_shot && obs_xy && n_shots > 0 && n_cams > 0),
-               OSFM_E_INVALID, "%s: null argument", who);
-  for (int c = 0; c < n_cams; c++)
-    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
-                 c, cam_model[c]);
-  for (int s = 0; s < n_shots; s++)
-    OSFM_REQUIRE(shot_camera[s] >= 0 && shot_camera[s] < n_cams, OSFM_E_INVALID, "%s: shot %d names a camera outside the table", who, s);
   OSFM_CTX_LOCK(ctx);
-  OSFM_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t sizes[] = {(size_t)n_shots * 96, (size_t)n_shots * 4, (size_t)n_cams * 4, (size_t)n_cams * 128, (size_t)n_obs * 4, (size_t)n_obs * 16};
-  const void *src[] = {shot_pose, shot_camera, cam_model, cam_params, obs_shot, obs_xy};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
+  PixelRows rows;
   OsfmPoolBuf in;
-  OSFM_HIP(in.alloc(ctx, arena_bytes));
-  char *base = (char *)in.p;
-  for (int i = 0; i < kBuffers; i++)
-    if (sizes[i]) OSFM_HIP(hipMemcpyAsync(base + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st));
-  const PixelRows rows{(const double *)(base + offs[0]), (const int32_t *)(base + offs[1]), (const int32_t *)(base + offs[2]),
-                       (const double *)(base + offs[3]), (const int32_t *)(base + offs[4]), (const double *)(base + offs[5]), n_shots};
+  OSFM_TRY(upload_pixel_rows(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, n_obs, in, &rows, who));
+  hipStream_t st = ctx->stream;
   return run_device(ctx, st, rows, track_offsets, n_tracks, params, nullptr, points, status, iterations_used, kernel_ms, who);
 }
 
@@ -364,4 +542,52 @@ extern "C" int osfm_triangulate_refine(osfm_ctx *ctx, const double *centers, con
   std::vector<uint8_t> status((size_t)(n_tracks > 0 ? n_tracks : 0));
   return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, &p, n_tracks > 0 ? initial : nullptr, points, status.data(),
                        iterations_used, kernel_ms, who);
+}
+
+extern "C" int osfm_triangulate_bearings_robust(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets,
+                                                int n_tracks, const osfm_triangulate_params *params, const double *draws, uint64_t seed,
+                                                double *points, uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers, int32_t *tries_used,
+                                                double *kernel_ms) {
+  const char *who = "osfm_triangulate_bearings_robust";
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  if (n_tracks == 0) return OSFM_OK;
+  const int64_t n_obs = track_offsets[n_tracks];
+  const RobustResults res{points, status, inlier_mask, n_inliers, tries_used};
+  OSFM_TRY(check_robust_results(res, n_obs, who));
+  OSFM_REQUIRE(n_obs == 0 || (centers && bearings), OSFM_E_INVALID, "%s: null centers / bearings", who);
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  OsfmPoolBuf in;
+  const size_t bytes = ((size_t)n_obs * 24 + 255) / 256 * 256;
+  OSFM_HIP(in.alloc(ctx, 2 * bytes));
+  double *d_centers = (double *)in.p, *d_bearings = (double *)((char *)in.p + bytes);
+  if (n_obs) {
+    OSFM_HIP(hipMemcpyAsync(d_centers, centers, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
+    OSFM_HIP(hipMemcpyAsync(d_bearings, bearings, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
+  }
+  return run_device_robust(ctx, st, BearingRows{d_centers, d_bearings}, track_offsets, n_tracks, params, draws, seed, res, kernel_ms, who);
+}
+
+extern "C" int osfm_triangulate_tracks_robust(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots,
+                                              const int32_t *cam_model, const double *cam_params, int n_cams, const int32_t *obs_shot,
+                                              const double *obs_xy, const int64_t *track_offsets, int n_tracks,
+                                              const osfm_triangulate_params *params, const double *draws, uint64_t seed, double *points,
+                                              uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers, int32_t *tries_used, double *kernel_ms) {
+  const char *who = "osfm_triangulate_tracks_robust";
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  OSFM_REQUIRE(n_shots >= 0 && n_cams >= 0, OSFM_E_INVALID, "%s: negative size", who);
+  if (n_tracks == 0) return OSFM_OK;
+  const int64_t n_obs = track_offsets[n_tracks];
+  const RobustResults res{points, status, inlier_mask, n_inliers, tries_used};
+  OSFM_TRY(check_robust_results(res, n_obs, who));
+  OSFM_CTX_LOCK(ctx);
+  PixelRows rows;
+  OsfmPoolBuf in;
+  OSFM_TRY(upload_pixel_rows(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, n_obs, in, &rows, who));
+  return run_device_robust(ctx, ctx->stream, rows, track_offsets, n_tracks, params, draws, seed, res, kernel_ms, who);
 }

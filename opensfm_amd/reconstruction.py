@@ -7,8 +7,8 @@ one call, counts the rotation-only inliers and the reconstructability on the dev
 does (``np.argsort(-np.array(score))``).
 
 ``triangulate_shot_features(tracks_manager, reconstruction, shot_ids, config)`` and ``retriangulate(tracks_manager, reconstruction, config)``
-(``reconstruction.py:1143-1226``) triangulate every track of their batch in one GPU call (``triangulate.hip``, ``triangulation_type: FULL``);
-``triangulate_bearings_arrays`` / ``triangulate_tracks_arrays`` are the same call on flat arrays.
+(``reconstruction.py:1143-1226``) triangulate every track of their batch in one GPU call (``triangulate.hip``, ``triangulation_type: FULL``, or ``ROBUST`` when ``robust_seed`` or ``robust_draws`` says where the draws come from);
+``triangulate_bearings_arrays`` / ``triangulate_tracks_arrays`` and their ``_robust`` forms are the same calls on flat arrays.
 
 ``resect(data, tracks_manager, reconstruction, shot_id, threshold, min_inliers)`` (``reconstruction.py:695-762``) adds one image to the map
 with the absolute-pose LO-RANSAC of ``abspose.hip``; ``resect_candidates`` is the candidate loop of ``grow_reconstruction``
@@ -208,7 +208,9 @@ def cull_final_point_cloud(reconstruction, config: Dict[str, Any]) -> Dict[str, 
 # ------------------------------------------------------------------------------------------------
 # triangulation of tracks (reconstruction.py:1032-1226)
 # ------------------------------------------------------------------------------------------------
-TRIANGULATION_STATUS = ("triangulated", "fewer than 2 observations", "ray angle", "reprojection angle", "depth", "result not finite")
+TRIANGULATION_STATUS = ("triangulated", "fewer than 2 observations", "ray angle", "reprojection angle", "depth", "result not finite",
+                        "no consensus")  # (2 .. 4: FULL only; 6: ROBUST only)
+ROBUST_TRIES = 11
 
 
 def _triangulate_params(threshold: float, min_angle_deg: float, min_depth: float, refinement_iterations: int) -> TriangulateParams:
@@ -266,18 +268,97 @@ def triangulate_tracks_arrays(shot_pose: np.ndarray, shot_camera: np.ndarray, ca
     return points[:n_tracks], status[:n_tracks], iterations[:n_tracks], ms.value
 
 
-def _triangulate_into(tracks_manager, reconstruction, track_ids: List[str], config: Dict[str, Any], ctx=None) -> None:
+def _robust_draws(draws, n_tracks: int, who: str):
+    """-> (the (n_tracks, 11) float64 array or None, its pointer or a null one)"""
+    if draws is None:
+        return None, C.POINTER(C.c_double)()
+    draws = np.ascontiguousarray(draws, np.float64).reshape(-1, ROBUST_TRIES)
+    if len(draws) != n_tracks:
+        raise ValueError(who + ": draws must be n_tracks x %d" % ROBUST_TRIES)
+    return draws, _fptr(draws, C.c_double)
+
+
+def _robust_outputs(n_tracks: int, n_obs: int):
+    return (np.full((max(n_tracks, 1), 3), np.nan), np.zeros(max(n_tracks, 1), np.uint8), np.zeros(max(n_obs, 1), np.uint8),
+            np.zeros(max(n_tracks, 1), np.int32), np.zeros(max(n_tracks, 1), np.int32), C.c_double(0.0))
+
+
+def triangulate_bearings_arrays_robust(centers: np.ndarray, bearings: np.ndarray, track_offsets: Sequence[int], threshold: float = 0.006,
+                                       min_angle_deg: float = 1.0, min_depth: float = 0.001, refinement_iterations: int = 10, draws=None,
+                                       seed: int = 0, ctx=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, float]:
+    """``osfm_triangulate_bearings_robust`` (TrackTriangulator.triangulate_robust per track): `draws` (n_tracks, 11) in [0, 1), or None for
+    the library's generator over (seed, track, try).  -> (points (n, 3), NaN unless triangulated; status (n,): 0, 1, 5 or 6 of
+    TRIANGULATION_STATUS; inlier_mask (n_obs,) uint8; n_inliers (n,); tries_used (n,); kernel milliseconds)."""
+    ctx = ctx or default_context()
+    centers = np.ascontiguousarray(centers, np.float64).reshape(-1, 3)
+    bearings = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(track_offsets, np.int64)
+    n_tracks = len(off) - 1
+    if len(centers) != len(bearings) or n_tracks < 0 or (n_tracks > 0 and off[-1] != len(centers)):
+        raise ValueError("triangulate_bearings_arrays_robust: centers / bearings / track_offsets do not agree")
+    draws, draws_ptr = _robust_draws(draws, n_tracks, "triangulate_bearings_arrays_robust")
+    prm = _triangulate_params(threshold, min_angle_deg, min_depth, refinement_iterations)
+    points, status, mask, n_inliers, tries, ms = _robust_outputs(n_tracks, len(centers))
+    check(load().osfm_triangulate_bearings_robust(ctx.handle, _fptr(centers, C.c_double), _fptr(bearings, C.c_double), _fptr(off, C.c_int64),
+                                                  n_tracks, C.byref(prm), draws_ptr, C.c_uint64(int(seed) & (2**64 - 1)), _fptr(points, C.c_double),
+                                                  _fptr(status, C.c_uint8), _fptr(mask, C.c_uint8), _fptr(n_inliers, C.c_int32),
+                                                  _fptr(tries, C.c_int32), C.byref(ms)), "osfm_triangulate_bearings_robust")
+    return points[:n_tracks], status[:n_tracks], mask[:len(centers)], n_inliers[:n_tracks], tries[:n_tracks], ms.value
+
+
+def triangulate_tracks_arrays_robust(shot_pose: np.ndarray, shot_camera: np.ndarray, cam_model: np.ndarray, cam_params: np.ndarray,
+                                     obs_shot: np.ndarray, obs_xy: np.ndarray, track_offsets: Sequence[int], threshold: float = 0.006,
+                                     min_angle_deg: float = 1.0, min_depth: float = 0.001, refinement_iterations: int = 10, draws=None,
+                                     seed: int = 0, ctx=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, float]:
+    """``osfm_triangulate_tracks_robust``: the same from (shot, normalised image point) rows, the tables as for triangulate_tracks_arrays."""
+    ctx = ctx or default_context()
+    shot_pose = np.ascontiguousarray(shot_pose, np.float64).reshape(-1, 12)
+    shot_camera = np.ascontiguousarray(shot_camera, np.int32)
+    cam_model = np.ascontiguousarray(cam_model, np.int32)
+    cam_params = np.ascontiguousarray(cam_params, np.float64).reshape(-1, 16)
+    obs_shot = np.ascontiguousarray(obs_shot, np.int32)
+    obs_xy = np.ascontiguousarray(np.asarray(obs_xy, np.float64).reshape(-1, 2))
+    off = np.ascontiguousarray(track_offsets, np.int64)
+    n_tracks = len(off) - 1
+    if (len(shot_camera) != len(shot_pose) or len(cam_params) != len(cam_model) or len(obs_shot) != len(obs_xy) or n_tracks < 0
+            or (n_tracks > 0 and off[-1] != len(obs_shot))):
+        raise ValueError("triangulate_tracks_arrays_robust: array lengths do not agree")
+    draws, draws_ptr = _robust_draws(draws, n_tracks, "triangulate_tracks_arrays_robust")
+    prm = _triangulate_params(threshold, min_angle_deg, min_depth, refinement_iterations)
+    points, status, mask, n_inliers, tries, ms = _robust_outputs(n_tracks, len(obs_shot))
+    check(load().osfm_triangulate_tracks_robust(ctx.handle, _fptr(shot_pose, C.c_double), _fptr(shot_camera, C.c_int32), len(shot_pose),
+                                                _fptr(cam_model, C.c_int32), _fptr(cam_params, C.c_double), len(cam_model),
+                                                _fptr(obs_shot, C.c_int32), _fptr(obs_xy, C.c_double), _fptr(off, C.c_int64), n_tracks,
+                                                C.byref(prm), draws_ptr, C.c_uint64(int(seed) & (2**64 - 1)), _fptr(points, C.c_double),
+                                                _fptr(status, C.c_uint8), _fptr(mask, C.c_uint8), _fptr(n_inliers, C.c_int32),
+                                                _fptr(tries, C.c_int32), C.byref(ms)), "osfm_triangulate_tracks_robust")
+    return points[:n_tracks], status[:n_tracks], mask[:len(obs_shot)], n_inliers[:n_tracks], tries[:n_tracks], ms.value
+
+
+def _triangulate_into(tracks_manager, reconstruction, track_ids: List[str], config: Dict[str, Any], ctx=None, *, robust_seed=None,
+                      robust_draws=None) -> None:
     """TrackTriangulator.triangulate for every track of `track_ids` in one call: the observations of a track in the shots of the
-    reconstruction, in the order the manager returns them; every accepted track becomes a point that all of them observe."""
+    reconstruction, in the order the manager returns them; every accepted track becomes a point that all of them observe.
+    ``triangulation_type: ROBUST`` is TrackTriangulator.triangulate_robust in one call, and needs to be told where its draws come from:
+    `robust_seed` (the library's generator; track k of `track_ids` draws as track k) or `robust_draws` (len(track_ids) x 11 values in
+    [0, 1), row k for track k).  Only a track's best inliers then observe its point."""
     threshold = config["triangulation_threshold"]
     min_ray_angle = config["triangulation_min_ray_angle"]
     min_depth = config["triangulation_min_depth"]
     refinement_iterations = config["triangulation_refinement_iterations"]
     kind = config["triangulation_type"]
-    if kind == "ROBUST":
-        raise NotImplementedError("triangulation_type ROBUST draws from numpy's global generator over an unordered set of tracks: it has no "
-                                  "reproducible result, and the GPU path implements FULL only")
-    if kind != "FULL" or not track_ids:  # (the reference does nothing for any other value)
+    robust = kind == "ROBUST"
+    if robust and robust_seed is None and robust_draws is None:
+        raise NotImplementedError("triangulation_type ROBUST draws from numpy's global generator over an unordered set of tracks in the "
+                                  "reference: it has no reproducible result there.  Pass robust_seed= (the library's per-track generator) "
+                                  "or robust_draws= (len(track_ids) x 11 values in [0, 1)) to run it on the GPU")
+    if robust and robust_seed is not None and robust_draws is not None:
+        raise ValueError("robust_seed and robust_draws exclude each other")
+    if robust and robust_draws is not None:
+        robust_draws = np.asarray(robust_draws, np.float64).reshape(-1, ROBUST_TRIES)
+        if len(robust_draws) != len(track_ids):
+            raise ValueError("robust_draws must hold %d values for each of the call's %d tracks" % (ROBUST_TRIES, len(track_ids)))
+    if kind not in ("FULL", "ROBUST") or not track_ids:  # (the reference does nothing for any other value)
         return
     shots = reconstruction.shots
     shot_index: Dict[str, int] = {}
@@ -314,34 +395,44 @@ def _triangulate_into(tracks_manager, reconstruction, track_ids: List[str], conf
     offsets = np.r_[0, np.cumsum([len(m) for m in members])].astype(np.int64)
     if not poses:  # no track has an observation in the reconstruction
         return
-    points, status, _, _ = triangulate_tracks_arrays(np.array(poses), np.array(shot_camera, np.int32), np.array(models, np.int32),
-                                                     np.array(params, np.float64).reshape(-1, 16), np.array(obs_shot, np.int32),
-                                                     np.array(obs_xy, np.float64).reshape(-1, 2), offsets, threshold, min_ray_angle, min_depth,
-                                                     refinement_iterations, ctx=ctx)
-    for track, ids, X, st in zip(track_ids, members, points, status):
+    tables = (np.array(poses), np.array(shot_camera, np.int32), np.array(models, np.int32), np.array(params, np.float64).reshape(-1, 16),
+              np.array(obs_shot, np.int32), np.array(obs_xy, np.float64).reshape(-1, 2), offsets, threshold, min_ray_angle, min_depth,
+              refinement_iterations)
+    if robust:
+        points, status, mask, _, _, _ = triangulate_tracks_arrays_robust(*tables, draws=robust_draws, seed=robust_seed or 0, ctx=ctx)
+    else:
+        points, status, _, _ = triangulate_tracks_arrays(*tables, ctx=ctx)
+        mask = np.ones(len(obs_shot), np.uint8)
+    for k, (track, ids, X, st) in enumerate(zip(track_ids, members, points, status)):
         if st != 0:
             continue
         reconstruction.create_point(track, X.tolist())
-        for shot_id in ids:
-            reconstruction.add_observation(shot_id, track, tracks_manager.get_observation(shot_id, track))
+        for shot_id, inlier in zip(ids, mask[offsets[k]:offsets[k + 1]]):
+            if inlier:
+                reconstruction.add_observation(shot_id, track, tracks_manager.get_observation(shot_id, track))
 
 
-def triangulate_shot_features(tracks_manager, reconstruction, shot_ids, config: Dict[str, Any], ctx=None) -> None:
+def triangulate_shot_features(tracks_manager, reconstruction, shot_ids, config: Dict[str, Any], ctx=None, *, robust_seed=None,
+                              robust_draws=None) -> None:
     """Reconstruct as many tracks seen in `shot_ids` as possible (``reconstruction.py:1143-1183``): the tracks of those shots that the
-    reconstruction does not hold yet, one GPU call.  ``triangulation_type`` FULL; ROBUST raises NotImplementedError."""
+    reconstruction does not hold yet, one GPU call.  ``triangulation_type`` FULL, or ROBUST with `robust_seed` or `robust_draws` (see
+    _triangulate_into; the call's track list is the tracks of `shot_ids` in the given order of the shots, each shot's in the manager's
+    order, first sighting, minus the points the map holds); ROBUST with neither raises NotImplementedError."""
     all_shots_ids = set(tracks_manager.get_shot_ids())
     tracks_ids = dict.fromkeys(t for s in shot_ids if s in all_shots_ids for t in tracks_manager.get_shot_observations(s))
-    _triangulate_into(tracks_manager, reconstruction, [t for t in tracks_ids if t not in reconstruction.points], config, ctx)
+    _triangulate_into(tracks_manager, reconstruction, [t for t in tracks_ids if t not in reconstruction.points], config, ctx,
+                      robust_seed=robust_seed, robust_draws=robust_draws)
 
 
-def retriangulate(tracks_manager, reconstruction, config: Dict[str, Any], ctx=None) -> Dict[str, Any]:
+def retriangulate(tracks_manager, reconstruction, config: Dict[str, Any], ctx=None, *, robust_seed=None, robust_draws=None) -> Dict[str, Any]:
     """Retriangulate all points (``reconstruction.py:1186-1226``): the map's points are dropped and every track seen by its shots goes
-    through one GPU call.  -> {"num_points_before", "num_points_after", "wall_time"}"""
+    through one GPU call (the track list: the tracks of the reconstruction's shots in map order, first sighting).  ROBUST as for
+    triangulate_shot_features.  -> {"num_points_before", "num_points_after", "wall_time"}"""
     start = time.perf_counter()
     report: Dict[str, Any] = {"num_points_before": len(reconstruction.points)}
     for key in ("triangulation_threshold", "triangulation_min_ray_angle", "triangulation_min_depth", "triangulation_refinement_iterations"):
         config[key]  # read before the map is touched, as the reference does
-    if config["triangulation_type"] == "ROBUST":
+    if config["triangulation_type"] == "ROBUST" and robust_seed is None and robust_draws is None:
         _triangulate_into(tracks_manager, reconstruction, [], config, ctx)  # raises
     if hasattr(reconstruction, "remove_landmark"):
         for lm_id in list(reconstruction.points):
@@ -351,7 +442,7 @@ def retriangulate(tracks_manager, reconstruction, config: Dict[str, Any], ctx=No
     all_shots_ids = set(tracks_manager.get_shot_ids())
     tracks = dict.fromkeys(t for image in reconstruction.shots.keys() if image in all_shots_ids
                            for t in tracks_manager.get_shot_observations(image).keys())
-    _triangulate_into(tracks_manager, reconstruction, list(tracks), config, ctx)
+    _triangulate_into(tracks_manager, reconstruction, list(tracks), config, ctx, robust_seed=robust_seed, robust_draws=robust_draws)
     report["num_points_after"] = len(reconstruction.points)
     report["wall_time"] = time.perf_counter() - start
     return report

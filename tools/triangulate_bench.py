@@ -5,14 +5,17 @@ Workload (defaults): synthetic.make_ba_scene(5000, 500000, 10) -- 5 000 shots, 5
 has work to do.  ``--ragged`` takes the scene's ragged tracks instead (lengths 2 + Poisson(8), 15 % of the sightings missing), which
 puts tracks on both kernels.
 
-    python tools/triangulate_bench.py [--shots 5000] [--tracks 500000] [--track 10] [--ragged] [--steps 5] [--small 3000] [--no-host]
+    python tools/triangulate_bench.py [--shots 5000] [--tracks 500000] [--track 10] [--ragged] [--steps 5] [--small 3000] [--no-host] [--robust]
 
 Prints one JSON line.  "retriangulate": the whole workload in one call, as reconstruction.retriangulate issues it -- kernel milliseconds
 (HIP events), end-to-end milliseconds of the array call (uploads and downloads included), tracks per second of kernel time, and the
 fraction of the HBM bound the kernel time amounts to (20 B read per observation, 32 B written per track, at --hbm-tbs).  "shot_features":
 the first --small tracks, the size of a triangulate_shot_features call after one resected image.  "host": the same --small call through
 the HOST BUILD of triangulate.hip (tests/native/build_triangulate_emu.py: the same kernels on one CPU thread, lanes as fibres -- an
-emulation made for testing, not an optimised CPU implementation), with whether its results equal the GPU's."""
+emulation made for testing, not an optimised CPU implementation), with whether its results equal the GPU's.
+``--robust`` adds "robust": the same two calls through osfm_triangulate_tracks_robust (`triangulation_type: ROBUST`, the library's
+generator with --seed) beside the FULL figures of the same build and scene, with the mean tries_used and inlier share, so that the
+cost per try can be read off."""
 from __future__ import annotations
 
 import argparse
@@ -61,6 +64,28 @@ def call(sc, ctx=None):
     out = reconstruction.triangulate_tracks_arrays(sc["shot_pose"], sc["shot_camera"], sc["cam_model"], sc["cam_params"], sc["obs_shot"], sc["obs_xy"],
                                                    sc["offsets"], ctx=ctx)
     return out, 1e3 * (time.perf_counter() - t0)
+
+
+def call_robust(sc, seed, ctx=None):
+    t0 = time.perf_counter()
+    out = reconstruction.triangulate_tracks_arrays_robust(sc["shot_pose"], sc["shot_camera"], sc["cam_model"], sc["cam_params"], sc["obs_shot"],
+                                                          sc["obs_xy"], sc["offsets"], seed=seed, ctx=ctx)
+    return out, 1e3 * (time.perf_counter() - t0)
+
+
+def measure_robust(sc, steps, seed, ctx):
+    kernel, wall = [], []
+    for _ in range(steps):
+        out, ms = call_robust(sc, seed, ctx)
+        kernel.append(out[5])
+        wall.append(ms)
+    n_tracks, n_obs = len(sc["offsets"]) - 1, len(sc["obs_shot"])
+    k = float(np.median(kernel))
+    tries = float(out[4].sum())
+    return out, {"tracks": n_tracks, "observations": n_obs, "kernel_ms": k, "kernel_ms_min": float(np.min(kernel)), "wall_ms": float(np.median(wall)),
+                 "tracks_per_s": n_tracks / (k * 1e-3), "status_counts": np.bincount(out[1], minlength=7).tolist(),
+                 "mean_tries_used": tries / max(n_tracks, 1), "kernel_us_per_1000_tries": 1e6 * k / max(tries, 1.0),
+                 "inlier_share_of_triangulated": float(out[3].sum()) / max(float(np.diff(sc["offsets"])[out[1] == 0].sum()), 1.0)}
 
 
 def measure(sc, steps, hbm_tbs, ctx):
@@ -118,6 +143,8 @@ def main() -> None:
     ap.add_argument("--small", type=int, default=3000)
     ap.add_argument("--hbm-tbs", type=float, default=8.0, help="HBM bandwidth the bound is computed with, TB/s (MI355X: 8)")
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--robust", action="store_true", help="also measure osfm_triangulate_tracks_robust on the same scene")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the robust call's generator")
     a = ap.parse_args()
     ctx = _lib.default_context()
     sc = workload(a.shots, a.tracks, a.track, a.ragged)
@@ -130,6 +157,14 @@ def main() -> None:
     small_out, out["shot_features"] = measure(small, a.steps, a.hbm_tbs, ctx)
     again, _ = call(small, ctx)
     out["two_runs_bit_equal"] = bool(all(x.tobytes() == y.tobytes() for x, y in zip(again[:3], small_out[:3])))
+    if a.robust:
+        call_robust(small, a.seed, ctx)  # warm-up
+        call_robust(sc, a.seed, ctx)
+        out["robust"] = {}
+        _, out["robust"]["retriangulate"] = measure_robust(sc, a.steps, a.seed, ctx)
+        first, out["robust"]["shot_features"] = measure_robust(small, a.steps, a.seed, ctx)
+        again, _ = call_robust(small, a.seed, ctx)
+        out["robust"]["two_runs_bit_equal"] = bool(all(x.tobytes() == y.tobytes() for x, y in zip(again[:5], first[:5])))
     if not a.no_host:
         out["host"] = host_build(small, small_out)
     print(json.dumps(out))
