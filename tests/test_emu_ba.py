@@ -99,14 +99,14 @@ def test_straight_line_iteration_equals_the_careful_path(monkeypatch):
     cameras) and the generic rows"""
     from opensfm_amd import bundle
 
-    def runs(solve, pr, iters):
+    def runs(solve, pr, iters, envs=({"OSFM_BA_NO_FAST": "1"}, {}, {"OSFM_BA_FAST_FAIL_AT": "2"}), **cfg):
         out = []
-        for env in ({"OSFM_BA_NO_FAST": "1"}, {}, {"OSFM_BA_FAST_FAIL_AT": "2"}):
+        for env in envs:
             with monkeypatch.context() as mp:
                 for k, v in env.items():
                     mp.setenv(k, v)
                 with emulated():
-                    out.append(solve(pr, {"bundle_max_iterations": iters}, **NO_TOL))
+                    out.append(solve(pr, dict(cfg, bundle_max_iterations=iters), **NO_TOL))
         return out
 
     pr = synthetic.make_ba_scene(20, 300, 5, seed=11)
@@ -123,6 +123,16 @@ def test_straight_line_iteration_equals_the_careful_path(monkeypatch):
     careful, fast, failed = runs(bundle.bundle_general_arrays, prg, 3)
     for g in (fast, failed):
         assert np.array_equal(g["cost_history"], careful["cost_history"]) and np.array_equal(g["rig_instance_pose"], careful["rig_instance_pose"])
+    # a forced failure on an iteration that is also rejected, right behind another rejection (tests/ba_recovery_cases.py: the oracle rejects
+    # iterations 4, 5 and 7 of this scene's first eight): the blocks go back twice in one iteration, the second time from the careful path
+    import ba_recovery_cases as rc
+
+    careful, failed = runs(bundle.bundle_arrays, rc.problem("narrow20"), 8, envs=({"OSFM_BA_NO_FAST": "1"}, {"OSFM_BA_FAST_FAIL_AT": "5"}),
+                           loss_function=rc.config("narrow20")["loss_function"])
+    assert rc.rejected(careful["cost_history"]) == [i for i in rc.recorded("narrow20") if i <= 8] == [4, 5, 7]
+    assert failed["iterations"] == careful["iterations"] == 8 and failed["successful_steps"] == careful["successful_steps"] == 5
+    for k in ("cost_history", "shot_pose", "points", "cam_params"):
+        assert np.array_equal(failed[k], careful[k]), k
 
 
 @pytest.mark.skipif(not os.environ.get("OSFM_SLOW_TESTS"), reason="seven minutes on the emulation (hundreds of block-Jacobi CG iterations, a barrier tree per mat-vec); "
