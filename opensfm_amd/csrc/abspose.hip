@@ -10,7 +10,6 @@
 #include "lo_batch.h"
 
 using namespace osfm_ap;
-using osfm_rp::DevBuf;
 using osfm_rp::GpuWave;
 using osfm_rp::kWave;
 
@@ -90,7 +89,7 @@ extern "C" int osfm_abspose_images(osfm_ctx *ctx, const double *bearings, const 
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_b, d_X, d_off;
+  OsfmDevBuf d_b, d_X, d_off;
   OSFM_HIP(d_b.alloc((size_t)total * 24));
   OSFM_HIP(d_X.alloc((size_t)total * 24));
   OSFM_HIP(d_off.alloc((size_t)(n_images + 1) * 8));
@@ -111,16 +110,12 @@ extern "C" int osfm_abspose_images_pixels(osfm_ctx *ctx, const double *xy, const
   OSFM_TRY(check_args(offsets, n_images, prm, who));
   if (n_images == 0) return OSFM_OK;
   OSFM_REQUIRE(xy && points && results && image_cam && cam_model && cam_params && n_cams > 0, OSFM_E_INVALID, "%s: null argument", who);
-  for (int c = 0; c < n_cams; c++)
-    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d",
-                 who, c, cam_model[c]);
-  for (int p = 0; p < n_images; p++)
-    OSFM_REQUIRE(image_cam[p] >= 0 && image_cam[p] < n_cams, OSFM_E_INVALID, "%s: image %d names a camera outside the table", who, p);
+  OSFM_TRY(osfm_check_camera_table(cam_model, n_cams, image_cam, n_images, 1, "image", who));
   const int64_t total = offsets[n_images];
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_xy, d_b, d_X, d_off, d_ic, d_cm, d_cp;
+  OsfmDevBuf d_xy, d_b, d_X, d_off, d_ic, d_cm, d_cp;
   OSFM_HIP(d_xy.alloc((size_t)total * 16));
   OSFM_HIP(d_b.alloc((size_t)total * 24));
   OSFM_HIP(d_X.alloc((size_t)total * 24));
@@ -151,7 +146,7 @@ extern "C" int osfm_abspose_solve(osfm_ctx *ctx, const double *bearings, const d
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_b, d_X, d_m, d_c;
+  OsfmDevBuf d_b, d_X, d_m, d_c;
   OSFM_HIP(d_b.alloc((size_t)n * 24));
   OSFM_HIP(d_X.alloc((size_t)n * 24));
   OSFM_HIP(d_m.alloc(kMaxModels * 12 * 8));

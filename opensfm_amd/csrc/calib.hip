@@ -15,18 +15,6 @@ using namespace osfm_rp;
 
 namespace {
 
-struct DevBuf {  // frees on scope exit
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-  template <class T>
-  T *as() const {
-    return (T *)p;
-  }
-};
-
 // one workgroup per image: bearings of its features in the store's padded layout
 __global__ void store_bearings_kernel(const double *__restrict__ pts, const int64_t *__restrict__ tile_off, const int32_t *__restrict__ counts,
                                       const int32_t *__restrict__ cam_model, const double *__restrict__ cam_params, double *__restrict__ out) {
@@ -101,7 +89,7 @@ int osfm_store_bearings(osfm_ctx *ctx, const osfm_store *store, const int32_t *c
     OSFM_REQUIRE(cam_model[i] >= OSFM_CAMERA_PERSPECTIVE && cam_model[i] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "image %d: camera model %d", i,
                  cam_model[i]);
   const int64_t rows = (store->tile_off[n] + 4) * 32;
-  DevBuf d_model, d_par;
+  OsfmDevBuf d_model, d_par;
   double *d_b = nullptr;
   OSFM_HIP(d_model.alloc((size_t)n * 4));
   OSFM_HIP(d_par.alloc((size_t)n * 16 * 8));

@@ -416,11 +416,7 @@ extern "C" int osfm_points_conditioning(osfm_ctx *ctx, const double *points, int
   }
   OSFM_REQUIRE(shot_pose && shot_camera && cam_model && cam_params && obs_shot && obs_point && n_shots > 0 && n_cams > 0, OSFM_E_INVALID,
                "%s: null argument", who);
-  for (int c = 0; c < n_cams; c++)
-    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
-                 c, cam_model[c]);
-  for (int s = 0; s < n_shots; s++)
-    OSFM_REQUIRE(shot_camera[s] >= 0 && shot_camera[s] < n_cams, OSFM_E_INVALID, "%s: shot %d names a camera outside the table", who, s);
+  OSFM_TRY(osfm_check_camera_table(cam_model, n_cams, shot_camera, n_shots, 1, "shot", who));
   // stable counting sort by landmark
   std::vector<int64_t> start((size_t)n_points + 1, 0);
   for (int64_t i = 0; i < n_obs; i++) {
@@ -441,45 +437,42 @@ extern "C" int osfm_points_conditioning(osfm_ctx *ctx, const double *points, int
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t sizes[] = {(size_t)n_points * 24, (size_t)n_shots * 96,      (size_t)n_shots * 4,  (size_t)n_cams * 4,  (size_t)n_cams * 128,
-                          (size_t)n_obs * 4,     (size_t)n_obs * 4,         ((size_t)n_points + 1) * 8, (size_t)n_obs * 24, (size_t)n_obs * 48,
-                          (size_t)n_points * 8,  (size_t)n_points};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  double *d_points = (double *)(base + offs[0]), *d_pose = (double *)(base + offs[1]);
-  int32_t *d_shot_camera = (int32_t *)(base + offs[2]), *d_cam_model = (int32_t *)(base + offs[3]);
-  double *d_cam_params = (double *)(base + offs[4]);
-  int32_t *d_s_shot = (int32_t *)(base + offs[5]), *d_s_point = (int32_t *)(base + offs[6]);
-  int64_t *d_start = (int64_t *)(base + offs[7]);
-  double *d_rays = (double *)(base + offs[8]), *d_jtj = (double *)(base + offs[9]), *d_cond = (double *)(base + offs[10]);
-  uint8_t *d_reason = (uint8_t *)(base + offs[11]);
-  const void *src[] = {points, shot_pose, shot_camera, cam_model, cam_params, s_shot.data(), s_point.data(), start.data()};
-  for (int i = 0; i < 8; i++) OSFM_HIP(hipMemcpyAsync(base + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st));
+  OsfmArena A;
+  const auto d_points = A.add<double>((size_t)n_points * 3);
+  const auto d_pose = A.add<double>((size_t)n_shots * 12);
+  const auto d_shot_camera = A.add<int32_t>((size_t)n_shots);
+  const auto d_cam_model = A.add<int32_t>((size_t)n_cams);
+  const auto d_cam_params = A.add<double>((size_t)n_cams * 16);
+  const auto d_s_shot = A.add<int32_t>((size_t)n_obs);
+  const auto d_s_point = A.add<int32_t>((size_t)n_obs);
+  const auto d_start = A.add<int64_t>((size_t)n_points + 1);
+  const auto d_rays = A.add<double>((size_t)n_obs * 3);
+  const auto d_jtj = A.add<double>((size_t)n_obs * 6);
+  const auto d_cond = A.add<double>((size_t)n_points);
+  const auto d_reason = A.add<uint8_t>((size_t)n_points);
+  OSFM_HIP(A.alloc(ctx));
+  OSFM_HIP(A.upload(d_points, points, st));
+  OSFM_HIP(A.upload(d_pose, shot_pose, st));
+  OSFM_HIP(A.upload(d_shot_camera, shot_camera, st));
+  OSFM_HIP(A.upload(d_cam_model, cam_model, st));
+  OSFM_HIP(A.upload(d_cam_params, cam_params, st));
+  OSFM_HIP(A.upload(d_s_shot, s_shot.data(), st));
+  OSFM_HIP(A.upload(d_s_point, s_point.data(), st));
+  OSFM_HIP(A.upload(d_start, start.data(), st));
   const double rad = min_angle_deg * M_PI / 180.0;
   OSFM_HIP(hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(cond_obs_kernel, dim3((unsigned)((n_obs + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_points, d_pose, d_shot_camera,
-                     d_cam_model, d_cam_params, d_s_shot, d_s_point, n_obs, d_rays, d_jtj);
+  hipLaunchKernelGGL(cond_obs_kernel, dim3((unsigned)((n_obs + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_points, d_pose,
+                     d_shot_camera, d_cam_model, d_cam_params, d_s_shot, d_s_point, n_obs, d_rays, d_jtj);
   OSFM_HIP(hipGetLastError());
   constexpr int kPerBlock = kBlock / kGroup;
-  hipLaunchKernelGGL(cond_landmark_kernel, dim3((unsigned)((n_points + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_start, d_rays, d_jtj,
-                     n_obs, n_points, rad, cos(rad), min_abs_det, d_cond, d_reason);
+  hipLaunchKernelGGL(cond_landmark_kernel, dim3((unsigned)((n_points + kPerBlock - 1) / kPerBlock)), dim3(kBlock), 0, st, d_start, d_rays,
+                     d_jtj, n_obs, n_points, rad, cos(rad), min_abs_det, d_cond, d_reason);
   OSFM_HIP(hipGetLastError());
   OSFM_HIP(hipEventRecord(ctx->ev[1], st));
-  OSFM_HIP(hipMemcpyAsync(cond, d_cond, (size_t)n_points * 8, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(reason, d_reason, (size_t)n_points, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(cond, d_cond, d_cond.bytes, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(reason, d_reason, d_reason.bytes, hipMemcpyDeviceToHost, st));
   OSFM_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
+  OSFM_TRY(osfm_kernel_ms(ctx, kernel_ms));
   const double thr = stat_threshold(cond, reason, n_points, 1.0);
   int removed = 0;
   for (int i = 0; i < n_points; i++) {
@@ -585,22 +578,15 @@ extern "C" int osfm_points_isolation(osfm_ctx *ctx, const double *points, int n_
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t sizes[] = {(size_t)n * 16, ((size_t)n_cells + 1) * 4, (size_t)n * 8, (size_t)n * 4, 16};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  const CellPoint *d_pts = (const CellPoint *)(base + offs[0]);
-  const int32_t *d_cell_start = (const int32_t *)(base + offs[1]);
-  double *d_avg = (double *)(base + offs[2]);
-  int32_t *d_open = (int32_t *)(base + offs[3]), *d_count = (int32_t *)(base + offs[4]);
-  OSFM_HIP(hipMemcpyAsync(base + offs[0], sorted.data(), sizes[0], hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(base + offs[1], cell_start.data(), sizes[1], hipMemcpyHostToDevice, st));
+  OsfmArena A;
+  const auto d_pts = A.add<CellPoint>((size_t)n);
+  const auto d_cell_start = A.add<int32_t>((size_t)n_cells + 1);
+  const auto d_avg = A.add<double>((size_t)n);
+  const auto d_open = A.add<int32_t>((size_t)n);
+  const auto d_count = A.add<int32_t>(4);
+  OSFM_HIP(A.alloc(ctx));
+  OSFM_HIP(A.upload(d_pts, (const CellPoint *)sorted.data(), st));
+  OSFM_HIP(A.upload(d_cell_start, cell_start.data(), st));
   const int k1 = k + 1;
   double ms = 0.0;
   if (k1 <= 8)
@@ -609,7 +595,7 @@ extern "C" int osfm_points_isolation(osfm_ctx *ctx, const double *points, int n_
     OSFM_TRY(launch_knn<16>(ctx, st, d_pts, d_cell_start, g, n, k1, d_avg, d_open, d_count, &ms));
   else
     OSFM_TRY(launch_knn<32>(ctx, st, d_pts, d_cell_start, g, n, k1, d_avg, d_open, d_count, &ms));
-  OSFM_HIP(hipMemcpyAsync(avg, d_avg, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(avg, d_avg, d_avg.bytes, hipMemcpyDeviceToHost, st));
   OSFM_HIP(hipStreamSynchronize(st));
   if (kernel_ms) *kernel_ms = ms;
   const double thr = stat_threshold(avg, nullptr, n, 1.25);

@@ -78,16 +78,4 @@ struct GpuWave {  // one wavefront = one workgroup
   }
 };
 
-struct DevBuf {  // frees on scope exit
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-  template <class T>
-  T *as() const {
-    return (T *)p;
-  }
-};
-
 }  // namespace osfm_rp

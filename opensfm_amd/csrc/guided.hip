@@ -83,18 +83,6 @@ __global__ __launch_bounds__(kLanes) void guided_mutual_kernel(const int *__rest
   if (lane == 0) *out_n = c;
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-  template <class T>
-  T *as() const {
-    return (T *)p;
-  }
-};
-
 // float32 integer-valued descriptors in [0, 255] -> u8 + squared norms (host plumbing; the GPU path rejects anything else, as
 // osfm_store_upload_f32 does)
 bool to_u8(const float *f, int n, std::vector<uint8_t> &u, std::vector<int> &norm) {
@@ -131,7 +119,7 @@ extern "C" int osfm_match_guided(osfm_ctx *ctx, const float *f1, int n1, const f
                "osfm_match_guided: descriptors must be integer-valued in [0, 255] (cv2's float result depends on its SIMD build)");
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
-  DevBuf d_u1, d_u2, d_n1, d_n2, d_mask, d_b1, d_b2, d_rt, d_f6, d_s6, d_g12, d_g21, d_out, d_cnt;
+  OsfmDevBuf d_u1, d_u2, d_n1, d_n2, d_mask, d_b1, d_b2, d_rt, d_f6, d_s6, d_g12, d_g21, d_out, d_cnt;
   OSFM_HIP(d_u1.alloc(u1.size()));
   OSFM_HIP(d_u2.alloc(u2.size()));
   OSFM_HIP(d_n1.alloc((size_t)n1 * 4));

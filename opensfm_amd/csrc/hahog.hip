@@ -1253,7 +1253,7 @@ struct Slab {
   bool overflow = false;
   template <typename T>
   T *take(size_t n) {
-    const size_t bytes = ((n ? n : 1) * sizeof(T) + 255) / 256 * 256;
+    const size_t bytes = osfm_round256((n ? n : 1) * sizeof(T));
     if (used + bytes > buf.bytes) {
       overflow = true;
       return nullptr;
@@ -1263,7 +1263,7 @@ struct Slab {
     return p;
   }
 };
-inline size_t padded(size_t n, size_t elem) { return ((n ? n : 1) * elem + 255) / 256 * 256; }
+inline size_t padded(size_t n, size_t elem) { return osfm_round256((n ? n : 1) * elem); }
 
 inline dim3 grid2(int w, int h, int z = 1) { return dim3((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)z); }
 
@@ -1325,8 +1325,8 @@ static const TapPlan &tap_plan() {
   return plan;
 }
 static int hahog_tables(osfm_ctx *ctx, hipStream_t st, double **d_tab, DescTable **d_dtab, const float **d_taps) {
-  constexpr size_t n_tab = (size_t)kOrSide * kOrSide + 257, tab_bytes = (n_tab * sizeof(double) + 255) / 256 * 256;
-  constexpr size_t dt_bytes = (sizeof(DescTable) + 255) / 256 * 256;
+  constexpr size_t n_tab = (size_t)kOrSide * kOrSide + 257, tab_bytes = osfm_round256(n_tab * sizeof(double));
+  constexpr size_t dt_bytes = osfm_round256(sizeof(DescTable));
   const TapPlan &tp = tap_plan();
   std::lock_guard<std::mutex> g(ctx->hahog_mu);
   if (!ctx->d_hahog_tables) {

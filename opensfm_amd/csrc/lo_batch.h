@@ -57,46 +57,31 @@ int run_batch(osfm_ctx *ctx, hipStream_t st, const int64_t *d_off, const int64_t
   osfm_stop_tables(ctx, offsets, n_problems, prm->probability, minimal_samples, &stop, &stop_off);
   bool any_large = false;
   for (int p = 0; p < n_problems && !any_large; p++) any_large = offsets[p + 1] - offsets[p] > kLdsInliers;
-  const size_t sizes[] = {stop.size() * 8, stop_off.size() * 8, any_large ? (size_t)total * 4 : 4, (size_t)n_problems * result_bytes,
-                          mask0 ? (size_t)total : 1, mask1 ? (size_t)total : 1, 16};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  double *d_stop = (double *)(base + offs[0]);
-  int64_t *d_stopoff = (int64_t *)(base + offs[1]);
-  int *d_scratch = (int *)(base + offs[2]);
-  void *d_out = base + offs[3];
-  uint8_t *d_mask0 = mask0 ? (uint8_t *)(base + offs[4]) : nullptr;
-  uint8_t *d_mask1 = mask1 ? (uint8_t *)(base + offs[5]) : nullptr;
-  int *d_flag = (int *)(base + offs[6]);
-  OSFM_HIP(hipMemcpyAsync(d_stop, stop.data(), stop.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_stopoff, stop_off.data(), stop_off.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemsetAsync(d_flag, 0, 16, st));
-  const BatchArgs A{d_off, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), prm->inlier_chord, (int)prm->iterations, (int)prm->use_lo,
+  OsfmArena A;
+  const auto d_stop = A.add<double>(stop.size());
+  const auto d_stopoff = A.add<int64_t>(stop_off.size());
+  const auto d_scratch = A.add<int>(any_large ? (size_t)total : 1);
+  const auto d_out = A.add<char>((size_t)n_problems * result_bytes);
+  const auto d_mask0 = A.add<uint8_t>(mask0 ? (size_t)total : 1), d_mask1 = A.add<uint8_t>(mask1 ? (size_t)total : 1);
+  const auto d_flag = A.add<int>(4);
+  OSFM_HIP(A.alloc(ctx));
+  OSFM_HIP(A.upload(d_stop, stop.data(), st));
+  OSFM_HIP(A.upload(d_stopoff, stop_off.data(), st));
+  OSFM_HIP(hipMemsetAsync(d_flag, 0, d_flag.bytes, st));
+  const BatchArgs B{d_off, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), prm->inlier_chord, (int)prm->iterations, (int)prm->use_lo,
                     (int)prm->lo_iterations, (int)prm->use_iteration_reduction, d_scratch, d_flag};
   if (!timed_from_ev0) OSFM_HIP(hipEventRecord(ctx->ev[0], st));
-  launch(A, d_out, d_mask0, d_mask1);
+  launch(B, (void *)d_out.get(), mask0 ? d_mask0.get() : nullptr, mask1 ? d_mask1.get() : nullptr);
   OSFM_HIP(hipGetLastError());
   OSFM_HIP(hipEventRecord(ctx->ev[1], st));
   int flag = 0;
   OSFM_HIP(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(results, d_out, (size_t)n_problems * result_bytes, hipMemcpyDeviceToHost, st));
+  OSFM_HIP(hipMemcpyAsync(results, d_out, d_out.bytes, hipMemcpyDeviceToHost, st));
   if (mask0) OSFM_HIP(hipMemcpyAsync(mask0, d_mask0, (size_t)total, hipMemcpyDeviceToHost, st));
   if (mask1) OSFM_HIP(hipMemcpyAsync(mask1, d_mask1, (size_t)total, hipMemcpyDeviceToHost, st));
   OSFM_HIP(hipStreamSynchronize(st));
   OSFM_REQUIRE(flag == 0, OSFM_E_UNSUPPORTED, "%s: the tabulated mt19937 stream is too short for this input", who);
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
-  return OSFM_OK;
+  return osfm_kernel_ms(ctx, kernel_ms);
 }
 
 }  // namespace osfm_lo

@@ -263,6 +263,77 @@ struct OsfmPoolBuf {
   }
 };
 
+// A plain hipMalloc'd device buffer that is freed on scope exit (what a call does not take from the context's cache)
+struct OsfmDevBuf {
+  void *p = nullptr;
+  OsfmDevBuf() = default;
+  OsfmDevBuf(const OsfmDevBuf &) = delete;
+  OsfmDevBuf &operator=(const OsfmDevBuf &) = delete;
+  ~OsfmDevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
+  template <class T>
+  T *as() const {
+    return (T *)p;
+  }
+};
+
+// the step in which the sub-buffers of one device block are handed out
+constexpr size_t osfm_round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// The device buffers of one call, carved out of one block from the context's cache (the caller holds the context lock).  Two phases:
+// add<T>(count) declares a buffer and only counts -- the handle it returns knows the element type and the bytes asked for; after
+// alloc(ctx) the handle stands for the buffer wherever a T * is wanted (before: null).  Buffers lie in declaration order, each rounded
+// up to 256 bytes (none: no bytes).  The handles point back at the arena: it is neither copied nor moved.
+struct OsfmArena {
+  template <typename T>
+  struct Slot {
+    const OsfmArena *arena = nullptr;
+    size_t offset = 0, bytes = 0;
+    T *get() const { return arena && arena->block.p ? (T *)((char *)arena->block.p + offset) : nullptr; }
+    operator T *() const { return get(); }
+  };
+  OsfmPoolBuf block;
+  size_t total = 0;
+  OsfmArena() = default;
+  OsfmArena(const OsfmArena &) = delete;
+  OsfmArena &operator=(const OsfmArena &) = delete;
+  template <typename T>
+  Slot<T> add(size_t count) {
+    const Slot<T> s{this, total, count * sizeof(T)};
+    total += osfm_round256(s.bytes);
+    return s;
+  }
+  hipError_t alloc(osfm_ctx *ctx) { return block.alloc(ctx, total); }
+  // the whole of a buffer from the host, enqueued on st (an empty buffer: nothing)
+  template <typename T>
+  hipError_t upload(Slot<T> s, const T *src, hipStream_t st) const {
+    return s.bytes ? hipMemcpyAsync(s.get(), src, s.bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  }
+};
+
+// the time between ctx->ev[0] and ctx->ev[1] of a call whose stream has been synchronised, into *kernel_ms when it is wanted
+inline int osfm_kernel_ms(osfm_ctx *ctx, double *kernel_ms) {
+  if (!kernel_ms) return OSFM_OK;
+  float ms = 0.f;
+  OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  *kernel_ms = ms;
+  return OSFM_OK;
+}
+
+// The camera table of a pixel call: every model is one the kernels know, and each of `count` problems (`noun`: a "shot", an "image",
+// a "pair") names `per` cameras of the table in idx
+inline int osfm_check_camera_table(const int32_t *cam_model, int n_cams, const int32_t *idx, int count, int per, const char *noun,
+                                   const char *who) {
+  for (int c = 0; c < n_cams; c++)
+    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
+                 c, cam_model[c]);
+  for (int64_t i = 0; i < (int64_t)count * per; i++)
+    OSFM_REQUIRE(idx[i] >= 0 && idx[i] < n_cams, OSFM_E_INVALID, "%s: %s %d names a camera outside the table", who, noun, (int)(i / per));
+  return OSFM_OK;
+}
+
 #define OSFM_CTX_LOCK(ctx) std::lock_guard<std::recursive_mutex> osfm_ctx_lock_((ctx)->mu)
 
 // Per-device one-time hipFuncSetAttribute bookkeeping (attributes are per device, the flags must not be process-wide booleans)

@@ -162,14 +162,6 @@ __global__ void pixel_bearings_kernel(int model, CameraParams cam, const double 
   out[3 * i + 2] = b[2];
 }
 
-struct Sub {  // a slice of a DevBuf
-  void *p;
-  template <class T>
-  T *as() const {
-    return (T *)p;
-  }
-};
-
 constexpr int kRngTableSize = 1 << 21;  // raw outputs of std::mt19937(42): 1000 iterations with a full LO chain each need ~1.3e5
 
 // the context's device copy of the generator stream, made on first use
@@ -262,35 +254,43 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
   const int lo = prm->lo_iterations > 0 ? prm->lo_iterations : 1;
   // one device allocation for all work buffers of the batch (hipMalloc / hipFree are expensive and synchronising)
   const size_t cap5 = ((size_t)n_pairs * kMaxSlots + kWave - 1) / kWave * kWave;
-  const size_t sizes[] = {
-      (size_t)total * 24, (size_t)total * 24, stop.size() * 8, stop_off.size() * 8, (size_t)n_pairs * sizeof(PairState),
-      (size_t)n_pairs * kMaxSlots * 5 * 4, (size_t)n_pairs * kMaxSlots * 4, (size_t)n_pairs * kMaxSlots * 4, (size_t)n_pairs * kMaxSlots * 4,
-      (size_t)n_pairs * kMaxSlots * kMaxModels * 12 * 8, (size_t)n_pairs * lo * kLoSampleMax * 4, (size_t)n_pairs * lo * 4,
-      (size_t)n_pairs * lo * 4, (size_t)n_pairs * lo * 12 * 8, (size_t)total * 4, (size_t)total * 4, (size_t)n_pairs * kMaxSlots * 4,
-      (size_t)n_pairs * lo * 4, 4 * 4, cap5 * 60 * 8, cap5 * 36 * 8, cap5 * 4, cap5 * kMaxModels * 9 * 8, (size_t)n_pairs * lo * 9 * 8,
-      cap5 * kMaxModels * 8, cap5 * 4, cap5 * kMaxModels * 4};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;  // from the context's cache of blocks (the caller holds the context lock): a hipMalloc / hipFree of this size is ~2 ms per call
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  Sub sub[kBuffers];
-  for (int i = 0; i < kBuffers; i++) sub[i].p = (char *)arena.p + offs[i];
-  const Sub &d_u1 = sub[0], &d_u2 = sub[1], &d_stop = sub[2], &d_stopoff = sub[3], &d_st = sub[4], &d_sidx = sub[5], &d_posb = sub[6], &d_pos = sub[7],
-            &d_nm = sub[8], &d_models = sub[9], &d_lidx = sub[10], &d_lopos = sub[11], &d_look = sub[12], &d_lort = sub[13], &d_inl = sub[14],
-            &d_sub = sub[15], &d_l5 = sub[16], &d_lN = sub[17], &d_cnt = sub[18], &d_at6 = sub[19], &d_bas = sub[20], &d_ok5 = sub[21],
-            &d_E5 = sub[22], &d_loE = sub[23], &d_wr = sub[24], &d_nreal = sub[25], &d_valid = sub[26];
-  static_assert(kBuffers == 27, "buffer list and names must match");
-  OSFM_HIP(hipMemcpyAsync(d_stop.p, stop.data(), stop.size() * 8, hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_stopoff.p, stop_off.data(), stop_off.size() * 8, hipMemcpyHostToDevice, st));
-  Rounds R{d_b1, d_b2, d_u1.as<double>(), d_u2.as<double>(), d_off, n_pairs, d_stop.as<double>(), d_stopoff.as<int64_t>(), rng, 1.0 - cos(prm->threshold), (int)prm->iterations, (int)prm->use_lo,
-           (int)prm->lo_iterations, mode == OSFM_RELPOSE_MATCH ? 8 : 5, kMaxSlots, d_st.as<PairState>(), d_sidx.as<int>(), d_posb.as<int>(), d_pos.as<int>(),
-           d_nm.as<int>(), d_models.as<double>(), d_lidx.as<int>(), d_lopos.as<int>(), d_look.as<int>(), d_lort.as<double>(), d_inl.as<int>(),
-           d_at6.as<double>(), d_bas.as<double>(), d_ok5.as<int>(), d_E5.as<double>(), d_loE.as<double>(), d_l5.as<int>(), d_lN.as<int>(), d_cnt.as<int>(),
-           d_wr.as<double>(), d_nreal.as<int>(), d_valid.as<int>()};
+  const size_t slots = (size_t)n_pairs * kMaxSlots, los = (size_t)n_pairs * lo;
+  OsfmArena A;  // from the context's cache of blocks (the caller holds the context lock): a hipMalloc / hipFree of this size is ~2 ms per call
+  const auto d_u1 = A.add<double>((size_t)total * 3);
+  const auto d_u2 = A.add<double>((size_t)total * 3);
+  const auto d_stop = A.add<double>(stop.size());
+  const auto d_stopoff = A.add<int64_t>(stop_off.size());
+  const auto d_st = A.add<PairState>((size_t)n_pairs);
+  const auto d_sidx = A.add<int>(slots * 5);
+  const auto d_posb = A.add<int>(slots);
+  const auto d_pos = A.add<int>(slots);
+  const auto d_nm = A.add<int>(slots);
+  const auto d_models = A.add<double>(slots * kMaxModels * 12);
+  const auto d_lidx = A.add<int>(los * kLoSampleMax);
+  const auto d_lopos = A.add<int>(los);
+  const auto d_look = A.add<int>(los);
+  const auto d_lort = A.add<double>(los * 12);
+  const auto d_inl = A.add<int>((size_t)total);
+  const auto d_sub = A.add<int>((size_t)total);
+  const auto d_l5 = A.add<int>(slots);
+  const auto d_lN = A.add<int>(los);
+  const auto d_cnt = A.add<int>(4);
+  const auto d_at6 = A.add<double>(cap5 * 60);
+  const auto d_bas = A.add<double>(cap5 * 36);
+  const auto d_ok5 = A.add<int>(cap5);
+  const auto d_E5 = A.add<double>(cap5 * kMaxModels * 9);
+  const auto d_loE = A.add<double>(los * 9);
+  const auto d_wr = A.add<double>(cap5 * kMaxModels);
+  const auto d_nreal = A.add<int>(cap5);
+  const auto d_valid = A.add<int>(cap5 * kMaxModels);
+  OSFM_HIP(A.alloc(ctx));
+  OSFM_HIP(A.upload(d_stop, stop.data(), st));
+  OSFM_HIP(A.upload(d_stopoff, stop_off.data(), st));
+  Rounds R{d_b1, d_b2, d_u1, d_u2, d_off, n_pairs, d_stop, d_stopoff, rng, 1.0 - cos(prm->threshold), (int)prm->iterations, (int)prm->use_lo,
+           (int)prm->lo_iterations, mode == OSFM_RELPOSE_MATCH ? 8 : 5, kMaxSlots, d_st, d_sidx, d_posb, d_pos,
+           d_nm, d_models, d_lidx, d_lopos, d_look, d_lort, d_inl,
+           d_at6, d_bas, d_ok5, d_E5, d_loE, d_l5, d_lN, d_cnt,
+           d_wr, d_nreal, d_valid};
   // the side stream and its two events live in the context (creating and destroying them per call is ~1 ms: most of a single pair's call)
   if (!ctx->stream_c) OSFM_HIP(hipStreamCreateWithFlags(&ctx->stream_c, hipStreamNonBlocking));
   for (int q = 0; q < 2; q++)
@@ -305,13 +305,13 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
     const long items = std::max<long>(n_pairs, count);
     hipLaunchKernelGGL(rp_init_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, R, first, count);
   }
-  OSFM_HIP(hipMemsetAsync(d_cnt.p, 0, 16, st));
+  OSFM_HIP(hipMemsetAsync(d_cnt, 0, 16, st));
   int rounds = 0;
   for (;;) {
     int h[4] = {0, 0, 0, 0};
     hipLaunchKernelGGL(rp_walk_kernel, dim3(n_pairs), dim3(kWave), 0, st, R);
-    OSFM_HIP(hipMemcpyAsync(h, d_cnt.p, 16, hipMemcpyDeviceToHost, st));
-    OSFM_HIP(hipMemsetAsync(d_cnt.p, 0, 12, st));  // [3] (table overflow) is sticky
+    OSFM_HIP(hipMemcpyAsync(h, d_cnt, 16, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemsetAsync(d_cnt, 0, 12, st));  // [3] (table overflow) is sticky
     OSFM_HIP(hipStreamSynchronize(st));
     rounds++;
     OSFM_REQUIRE(h[3] == 0, OSFM_E_UNSUPPORTED, "osfm_relpose_pairs: the tabulated mt19937 stream (%d outputs) is too short for this input",
@@ -338,7 +338,7 @@ int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, c
     OSFM_HIP(hipGetLastError());
     OSFM_REQUIRE(rounds < 100000, OSFM_E_NUMERIC, "osfm_relpose_pairs: the rounds do not terminate");
   }
-  hipLaunchKernelGGL(rp_finish_kernel, dim3(n_pairs), dim3(kWave), 0, st, R, mode, prm->threshold, (int)prm->refine_iterations, d_sub.as<int>(), d_mask,
+  hipLaunchKernelGGL(rp_finish_kernel, dim3(n_pairs), dim3(kWave), 0, st, R, mode, prm->threshold, (int)prm->refine_iterations, d_sub, d_mask,
                      (PairOut *)d_out);
   OSFM_HIP(hipGetLastError());
   OSFM_HIP(hipStreamSynchronize(st));  // the work buffers above are released on return
@@ -361,7 +361,7 @@ extern "C" int osfm_pixel_bearings(osfm_ctx *ctx, int model, const double *cam, 
   if (n == 0) return OSFM_OK;
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
-  DevBuf d_px, d_out;
+  OsfmDevBuf d_px, d_out;
   OSFM_HIP(d_px.alloc((size_t)n * 16));
   OSFM_HIP(d_out.alloc((size_t)n * 24));
   OSFM_HIP(hipMemcpyAsync(d_px.p, px, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
@@ -394,7 +394,7 @@ extern "C" int osfm_relpose_pairs(osfm_ctx *ctx, const double *b1, const double 
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_b1, d_b2, d_off, d_mask, d_out;
+  OsfmDevBuf d_b1, d_b2, d_off, d_mask, d_out;
   OSFM_HIP(d_b1.alloc((size_t)total * 24));
   OSFM_HIP(d_b2.alloc((size_t)total * 24));
   OSFM_HIP(d_off.alloc((size_t)(n_pairs + 1) * 8));
@@ -421,10 +421,5 @@ extern "C" int osfm_relpose_pairs(osfm_ctx *ctx, const double *b1, const double 
   OSFM_HIP(hipMemcpyAsync(results, d_out.p, (size_t)n_pairs * sizeof(PairOut), hipMemcpyDeviceToHost, st));
   if (total) OSFM_HIP(hipMemcpyAsync(mask, d_mask.p, (size_t)total, hipMemcpyDeviceToHost, st));
   OSFM_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
-  return OSFM_OK;
+  return osfm_kernel_ms(ctx, kernel_ms);
 }

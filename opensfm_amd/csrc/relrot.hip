@@ -10,7 +10,6 @@
 #include "relrot_core.h"
 
 using namespace osfm_rr;
-using osfm_rp::DevBuf;
 using osfm_rp::GpuWave;
 using osfm_rp::kWave;
 
@@ -71,7 +70,7 @@ extern "C" int osfm_relrot_pairs(osfm_ctx *ctx, const double *b1, const double *
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_b1, d_b2, d_off;
+  OsfmDevBuf d_b1, d_b2, d_off;
   OSFM_HIP(d_b1.alloc((size_t)total * 24));
   OSFM_HIP(d_b2.alloc((size_t)total * 24));
   OSFM_HIP(d_off.alloc((size_t)(n_pairs + 1) * 8));
@@ -90,17 +89,12 @@ extern "C" int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const d
   if (n_pairs == 0) return OSFM_OK;
   OSFM_REQUIRE(p1 && p2 && results && pair_cams && cam_model && cam_params && n_cams > 0, OSFM_E_INVALID,
                "osfm_relrot_pairs_pixels: null argument");
-  for (int c = 0; c < n_cams; c++)
-    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID,
-                 "osfm_relrot_pairs_pixels: camera %d has model %d", c, cam_model[c]);
-  for (int p = 0; p < n_pairs; p++)
-    OSFM_REQUIRE(pair_cams[2 * p] >= 0 && pair_cams[2 * p] < n_cams && pair_cams[2 * p + 1] >= 0 && pair_cams[2 * p + 1] < n_cams, OSFM_E_INVALID,
-                 "osfm_relrot_pairs_pixels: pair %d names a camera outside the table", p);
+  OSFM_TRY(osfm_check_camera_table(cam_model, n_cams, pair_cams, n_pairs, 2, "pair", "osfm_relrot_pairs_pixels"));
   const int64_t total = offsets[n_pairs];
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DevBuf d_p1, d_p2, d_b1, d_b2, d_off, d_pc, d_cm, d_cp;
+  OsfmDevBuf d_p1, d_p2, d_b1, d_b2, d_off, d_pc, d_cm, d_cp;
   OSFM_HIP(d_p1.alloc((size_t)total * 16));
   OSFM_HIP(d_p2.alloc((size_t)total * 16));
   OSFM_HIP(d_b1.alloc((size_t)total * 24));

@@ -15,6 +15,7 @@
 //   _good_track = a second sort by (root rank, image) exposes repeated images as equal neighbours.
 // Everything else is scans (rocPRIM).  Bit-identical to oracle/tracks_oracle.c.
 #include <cstring>  // rocprim's texture iterator calls the host memset
+#include <deque>
 #include <memory>
 
 #include <rocprim/rocprim.hpp>
@@ -143,18 +144,14 @@ __global__ void emit_kernel(const int *segincl, const int *good, const int *trac
   o_feature[k] = (int)(node - off[im]);
 }
 
-struct DevBuf {
-  std::vector<void *> ptrs;
+struct BufList {  // the device buffers of a call, freed on scope exit; the first failed allocation sticks in err
+  std::deque<OsfmDevBuf> bufs;
   hipError_t err = hipSuccess;
   template <class T>
   T *alloc(size_t n) {
-    void *p = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&p, (n ? n : 1) * sizeof(T));
-    if (p) ptrs.push_back(p);
-    return (T *)p;
-  }
-  ~DevBuf() {
-    for (void *p : ptrs) (void)hipFree(p);
+    bufs.emplace_back();
+    if (err == hipSuccess) err = bufs.back().alloc(n * sizeof(T));
+    return bufs.back().as<T>();
   }
 };
 }  // namespace
@@ -186,7 +183,7 @@ extern "C" int osfm_tracks_create(osfm_ctx *ctx, const int32_t *edge_a, const in
     *out = owner.release();
     return OSFM_OK;
   }
-  DevBuf B;
+  BufList B;
   int *ea = B.alloc<int>(E), *eb = B.alloc<int>(E);
   long long *off = B.alloc<long long>((size_t)n_images + 1);
   unsigned *rank = B.alloc<unsigned>(N);

@@ -318,155 +318,194 @@ std::vector<int32_t> split_long(const int64_t *offsets, int n_tracks) {
   return long_tracks;
 }
 
-// Both kernels over rows that are on the device already; `uploaded` bytes of the arena hold the caller's inputs.  The caller holds the
-// context lock and has recorded nothing on ev[0] / ev[1].
-template <class Rows>
-int run_device(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p,
-               const double *initial, double *points, uint8_t *status, int32_t *iterations_used, double *kernel_ms, const char *who) {
-  const std::vector<int32_t> long_tracks = split_long(offsets, n_tracks);
-  const size_t n_long = long_tracks.size();
-  const size_t sizes[] = {((size_t)n_tracks + 1) * 8, n_long * 4, (size_t)n_tracks * 24, (size_t)n_tracks, (size_t)n_tracks * 4, 16,
-                          initial ? (size_t)n_tracks * 24 : 0};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
+// What the plain and the robust call differ in on the host side: the struct the kernels write through and its buffers in the arena,
+// the optional input (`initial` / `draws`), the mask, the pair of kernels, the way back and what a refusal says.
+struct PlainCall {
+  using DeviceOut = Out;
+  template <class Rows>
+  static constexpr auto group_kernel = &tri_group_kernel<Rows>;
+  template <class Rows>
+  static constexpr auto wave_kernel = &tri_wave_kernel<Rows>;
+  static constexpr const char *refusal = "%s: an observation names a shot outside the table, or it or its shot's pose is not finite";
+  const double *initial;  // n_tracks x 3, or null
+  double *points;
+  uint8_t *status;
+  int32_t *iterations_used;
+  OsfmArena::Slot<double> d_points, d_initial;
+  OsfmArena::Slot<uint8_t> d_status;
+  OsfmArena::Slot<int32_t> d_iterations;
+  int check(int64_t, const char *who) const {
+    OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
+    return OSFM_OK;
   }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  int64_t *d_off = (int64_t *)(base + offs[0]);
-  int32_t *d_long = (int32_t *)(base + offs[1]);
-  Out out{(double *)(base + offs[2]), (uint8_t *)(base + offs[3]), (int32_t *)(base + offs[4]), (int *)(base + offs[5]),
-          initial ? (const double *)(base + offs[6]) : nullptr};
-  if (initial) OSFM_HIP(hipMemcpyAsync(base + offs[6], initial, sizes[6], hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_off, offsets, sizes[0], hipMemcpyHostToDevice, st));
-  if (n_long) OSFM_HIP(hipMemcpyAsync(d_long, long_tracks.data(), sizes[1], hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemsetAsync(out.bad, 0, 16, st));
-  const Params prm{p->threshold, p->min_angle_deg * M_PI / 180.0, p->min_depth, (int)p->refinement_iterations};
-  OSFM_HIP(hipEventRecord(ctx->ev[0], st));
-  if (n_long < (size_t)n_tracks) {
-    hipLaunchKernelGGL((tri_group_kernel<Rows>), dim3((unsigned)((n_tracks + kGroupsPerBlock - 1) / kGroupsPerBlock)), dim3(kBlock), 0, st, rows,
-                       d_off, n_tracks, prm, out);
-    OSFM_HIP(hipGetLastError());
+  void declare(OsfmArena &A, size_t n_tracks, size_t) {
+    d_points = A.add<double>(3 * n_tracks);
+    d_status = A.add<uint8_t>(n_tracks);
+    d_iterations = A.add<int32_t>(n_tracks);
+    d_initial = A.add<double>(initial ? 3 * n_tracks : 0);
   }
-  if (n_long) {
-    hipLaunchKernelGGL((tri_wave_kernel<Rows>), dim3((unsigned)n_long), dim3(kWave), 0, st, rows, d_off, d_long, prm, out);
-    OSFM_HIP(hipGetLastError());
+  int stage(const OsfmArena &A, int *d_bad, hipStream_t st, Out *out) const {
+    OSFM_HIP(A.upload(d_initial, initial, st));
+    *out = Out{d_points, d_status, d_iterations, d_bad, initial ? d_initial.get() : nullptr};
+    return OSFM_OK;
   }
-  OSFM_HIP(hipEventRecord(ctx->ev[1], st));
-  int bad = 0;
-  OSFM_HIP(hipMemcpyAsync(&bad, out.bad, 4, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(points, out.points, sizes[2], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(status, out.status, sizes[3], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(iterations_used, out.iterations, sizes[4], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
+  int fetch(const Out &out, hipStream_t st) const {
+    OSFM_HIP(hipMemcpyAsync(points, out.points, d_points.bytes, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemcpyAsync(status, out.status, d_status.bytes, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemcpyAsync(iterations_used, out.iterations, d_iterations.bytes, hipMemcpyDeviceToHost, st));
+    return OSFM_OK;
   }
-  OSFM_REQUIRE(bad == 0, OSFM_E_INVALID, "%s: an observation names a shot outside the table, or it or its shot's pose is not finite", who);
-  return OSFM_OK;
-}
+};
 
-struct RobustResults {
+struct RobustCall {
+  using DeviceOut = RobustOut;
+  template <class Rows>
+  static constexpr auto group_kernel = &tri_group_robust_kernel<Rows>;
+  template <class Rows>
+  static constexpr auto wave_kernel = &tri_wave_robust_kernel<Rows>;
+  static constexpr const char *refusal =
+      "%s: an observation names a shot outside the table, it or its shot's pose is not finite, or a draw lies outside [0, 1)";
+  const double *draws;  // n_tracks x 11, or null
+  uint64_t seed;
   double *points;
   uint8_t *status, *inlier_mask;
   int32_t *n_inliers, *tries_used;
+  OsfmArena::Slot<double> d_points, d_draws;
+  OsfmArena::Slot<uint8_t> d_status, d_mask;
+  OsfmArena::Slot<int32_t> d_inliers, d_tries;
+  int check(int64_t n_obs, const char *who) const {
+    OSFM_REQUIRE(points && status && n_inliers && tries_used, OSFM_E_INVALID, "%s: null points / status / n_inliers / tries_used", who);
+    OSFM_REQUIRE(n_obs == 0 || inlier_mask, OSFM_E_INVALID, "%s: null inlier_mask", who);
+    return OSFM_OK;
+  }
+  void declare(OsfmArena &A, size_t n_tracks, size_t n_obs) {
+    d_points = A.add<double>(3 * n_tracks);
+    d_status = A.add<uint8_t>(n_tracks);
+    d_inliers = A.add<int32_t>(n_tracks);
+    d_tries = A.add<int32_t>(n_tracks);
+    d_mask = A.add<uint8_t>(n_obs);
+    d_draws = A.add<double>(draws ? kRobustTries * n_tracks : 0);
+  }
+  int stage(const OsfmArena &A, int *d_bad, hipStream_t st, RobustOut *out) const {
+    OSFM_HIP(A.upload(d_draws, draws, st));
+    if (d_mask.bytes) OSFM_HIP(hipMemsetAsync(d_mask, 0, d_mask.bytes, st));
+    *out = RobustOut{d_points, d_status, d_mask, d_inliers, d_tries, d_bad, draws ? d_draws.get() : nullptr, seed};
+    return OSFM_OK;
+  }
+  int fetch(const RobustOut &out, hipStream_t st) const {
+    OSFM_HIP(hipMemcpyAsync(points, out.points, d_points.bytes, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemcpyAsync(status, out.status, d_status.bytes, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemcpyAsync(n_inliers, out.n_inliers, d_inliers.bytes, hipMemcpyDeviceToHost, st));
+    OSFM_HIP(hipMemcpyAsync(tries_used, out.tries, d_tries.bytes, hipMemcpyDeviceToHost, st));
+    if (d_mask.bytes) OSFM_HIP(hipMemcpyAsync(inlier_mask, out.mask, d_mask.bytes, hipMemcpyDeviceToHost, st));
+    return OSFM_OK;
+  }
 };
 
-// run_device for the robust kernels: the same split and arena, plus the draws (when given) and the per-observation mask
-template <class Rows>
-int run_device_robust(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p,
-                      const double *draws, uint64_t seed, const RobustResults &res, double *kernel_ms, const char *who) {
+// Both kernels of `call` over rows that are on the device already.  The caller holds the context lock and has recorded nothing on
+// ev[0] / ev[1].
+template <class Rows, class Call>
+int run_device(osfm_ctx *ctx, hipStream_t st, const Rows &rows, const int64_t *offsets, int n_tracks, const osfm_triangulate_params *p, Call call,
+               double *kernel_ms, const char *who) {
   const std::vector<int32_t> long_tracks = split_long(offsets, n_tracks);
-  const size_t n_long = long_tracks.size(), n_obs = (size_t)offsets[n_tracks];
-  const size_t sizes[] = {((size_t)n_tracks + 1) * 8, n_long * 4, (size_t)n_tracks * 24, (size_t)n_tracks, (size_t)n_tracks * 4, (size_t)n_tracks * 4,
-                          16,                         n_obs,      draws ? (size_t)n_tracks * kRobustTries * 8 : 0};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OsfmPoolBuf arena;
-  OSFM_HIP(arena.alloc(ctx, arena_bytes));
-  char *base = (char *)arena.p;
-  int64_t *d_off = (int64_t *)(base + offs[0]);
-  int32_t *d_long = (int32_t *)(base + offs[1]);
-  RobustOut out{(double *)(base + offs[2]), (uint8_t *)(base + offs[3]), (uint8_t *)(base + offs[7]), (int32_t *)(base + offs[4]),
-                (int32_t *)(base + offs[5]), (int *)(base + offs[6]), draws ? (const double *)(base + offs[8]) : nullptr, seed};
-  if (draws) OSFM_HIP(hipMemcpyAsync(base + offs[8], draws, sizes[8], hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemcpyAsync(d_off, offsets, sizes[0], hipMemcpyHostToDevice, st));
-  if (n_long) OSFM_HIP(hipMemcpyAsync(d_long, long_tracks.data(), sizes[1], hipMemcpyHostToDevice, st));
-  OSFM_HIP(hipMemsetAsync(out.bad, 0, 16, st));
-  if (n_obs) OSFM_HIP(hipMemsetAsync(out.mask, 0, n_obs, st));
+  const size_t n_long = long_tracks.size();
+  OsfmArena A;
+  const auto d_off = A.add<int64_t>((size_t)n_tracks + 1);
+  const auto d_long = A.add<int32_t>(n_long);
+  const auto d_bad = A.add<int>(4);
+  call.declare(A, (size_t)n_tracks, (size_t)offsets[n_tracks]);
+  OSFM_HIP(A.alloc(ctx));
+  typename Call::DeviceOut out;
+  OSFM_TRY(call.stage(A, d_bad, st, &out));
+  OSFM_HIP(A.upload(d_off, offsets, st));
+  OSFM_HIP(A.upload(d_long, long_tracks.data(), st));
+  OSFM_HIP(hipMemsetAsync(out.bad, 0, d_bad.bytes, st));
   const Params prm{p->threshold, p->min_angle_deg * M_PI / 180.0, p->min_depth, (int)p->refinement_iterations};
   OSFM_HIP(hipEventRecord(ctx->ev[0], st));
   if (n_long < (size_t)n_tracks) {
-    hipLaunchKernelGGL((tri_group_robust_kernel<Rows>), dim3((unsigned)((n_tracks + kGroupsPerBlock - 1) / kGroupsPerBlock)), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL((Call::template group_kernel<Rows>), dim3((unsigned)((n_tracks + kGroupsPerBlock - 1) / kGroupsPerBlock)), dim3(kBlock), 0, st,
                        rows, d_off, n_tracks, prm, out);
     OSFM_HIP(hipGetLastError());
   }
   if (n_long) {
-    hipLaunchKernelGGL((tri_wave_robust_kernel<Rows>), dim3((unsigned)n_long), dim3(kWave), 0, st, rows, d_off, d_long, prm, out);
+    hipLaunchKernelGGL((Call::template wave_kernel<Rows>), dim3((unsigned)n_long), dim3(kWave), 0, st, rows, d_off, d_long, prm, out);
     OSFM_HIP(hipGetLastError());
   }
   OSFM_HIP(hipEventRecord(ctx->ev[1], st));
   int bad = 0;
   OSFM_HIP(hipMemcpyAsync(&bad, out.bad, 4, hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(res.points, out.points, sizes[2], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(res.status, out.status, sizes[3], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(res.n_inliers, out.n_inliers, sizes[4], hipMemcpyDeviceToHost, st));
-  OSFM_HIP(hipMemcpyAsync(res.tries_used, out.tries, sizes[5], hipMemcpyDeviceToHost, st));
-  if (n_obs) OSFM_HIP(hipMemcpyAsync(res.inlier_mask, out.mask, n_obs, hipMemcpyDeviceToHost, st));
+  OSFM_TRY(call.fetch(out, st));
   OSFM_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    OSFM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    *kernel_ms = ms;
-  }
-  OSFM_REQUIRE(bad == 0, OSFM_E_INVALID,
-               "%s: an observation names a shot outside the table, it or its shot's pose is not finite, or a draw lies outside [0, 1)", who);
-  return OSFM_OK;
-}
-
-int check_robust_results(const RobustResults &res, int64_t n_obs, const char *who) {
-  OSFM_REQUIRE(res.points && res.status && res.n_inliers && res.tries_used, OSFM_E_INVALID, "%s: null points / status / n_inliers / tries_used", who);
-  OSFM_REQUIRE(n_obs == 0 || res.inlier_mask, OSFM_E_INVALID, "%s: null inlier_mask", who);
+  OSFM_TRY(osfm_kernel_ms(ctx, kernel_ms));
+  OSFM_REQUIRE(bad == 0, OSFM_E_INVALID, Call::refusal, who);
   return OSFM_OK;
 }
 
 // the tables and rows of a pixel call, checked and on their way to the device (the caller holds the context lock; `in` owns the memory)
 int upload_pixel_rows(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
-                      const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy, int64_t n_obs, OsfmPoolBuf &in,
+                      const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy, int64_t n_obs, OsfmArena &in,
                       PixelRows *rows, const char *who) {
   OSFM_REQUIRE(n_obs == 0 || (shot_pose && shot_camera && cam_model && cam_params && obs_shot && obs_xy && n_shots > 0 && n_cams > 0),
                OSFM_E_INVALID, "%s: null argument", who);
-  for (int c = 0; c < n_cams; c++)
-    OSFM_REQUIRE(cam_model[c] >= OSFM_CAMERA_PERSPECTIVE && cam_model[c] <= OSFM_CAMERA_SPHERICAL, OSFM_E_INVALID, "%s: camera %d has model %d", who,
-                 c, cam_model[c]);
-  for (int s = 0; s < n_shots; s++)
-    OSFM_REQUIRE(shot_camera[s] >= 0 && shot_camera[s] < n_cams, OSFM_E_INVALID, "%s: shot %d names a camera outside the table", who, s);
+  OSFM_TRY(osfm_check_camera_table(cam_model, n_cams, shot_camera, n_shots, 1, "shot", who));
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const size_t sizes[] = {(size_t)n_shots * 96, (size_t)n_shots * 4, (size_t)n_cams * 4, (size_t)n_cams * 128, (size_t)n_obs * 4, (size_t)n_obs * 16};
-  const void *src[] = {shot_pose, shot_camera, cam_model, cam_params, obs_shot, obs_xy};
-  constexpr int kBuffers = sizeof(sizes) / sizeof(sizes[0]);
-  size_t offs[kBuffers], arena_bytes = 0;
-  for (int i = 0; i < kBuffers; i++) {
-    offs[i] = arena_bytes;
-    arena_bytes += (sizes[i] + 255) / 256 * 256;
-  }
-  OSFM_HIP(in.alloc(ctx, arena_bytes));
-  char *base = (char *)in.p;
-  for (int i = 0; i < kBuffers; i++)
-    if (sizes[i]) OSFM_HIP(hipMemcpyAsync(base + offs[i], src[i], sizes[i], hipMemcpyHostToDevice, st));
-  *rows = PixelRows{(const double *)(base + offs[0]), (const int32_t *)(base + offs[1]), (const int32_t *)(base + offs[2]),
-                    (const double *)(base + offs[3]), (const int32_t *)(base + offs[4]), (const double *)(base + offs[5]), n_shots};
+  const auto d_pose = in.add<double>((size_t)n_shots * 12);
+  const auto d_shot_camera = in.add<int32_t>((size_t)n_shots);
+  const auto d_cam_model = in.add<int32_t>((size_t)n_cams);
+  const auto d_cam_params = in.add<double>((size_t)n_cams * 16);
+  const auto d_obs_shot = in.add<int32_t>((size_t)n_obs);
+  const auto d_obs_xy = in.add<double>((size_t)n_obs * 2);
+  OSFM_HIP(in.alloc(ctx));
+  OSFM_HIP(in.upload(d_pose, shot_pose, st));
+  OSFM_HIP(in.upload(d_shot_camera, shot_camera, st));
+  OSFM_HIP(in.upload(d_cam_model, cam_model, st));
+  OSFM_HIP(in.upload(d_cam_params, cam_params, st));
+  OSFM_HIP(in.upload(d_obs_shot, obs_shot, st));
+  OSFM_HIP(in.upload(d_obs_xy, obs_xy, st));
+  *rows = PixelRows{d_pose, d_shot_camera, d_cam_model, d_cam_params, d_obs_shot, d_obs_xy, n_shots};
   return OSFM_OK;
+}
+
+// an entry point over bearings: the checks, centers and bearings to the device, then both kernels of `call`
+template <class Call>
+int bearings_call(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                  const osfm_triangulate_params *params, const Call &call, double *kernel_ms, const char *who) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  if (n_tracks == 0) return OSFM_OK;
+  const int64_t n_obs = track_offsets[n_tracks];
+  OSFM_TRY(call.check(n_obs, who));
+  OSFM_REQUIRE(n_obs == 0 || (centers && bearings), OSFM_E_INVALID, "%s: null centers / bearings", who);
+  OSFM_CTX_LOCK(ctx);
+  OSFM_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  OsfmArena in;
+  const auto d_centers = in.add<double>((size_t)n_obs * 3), d_bearings = in.add<double>((size_t)n_obs * 3);
+  OSFM_HIP(in.alloc(ctx));
+  OSFM_HIP(in.upload(d_centers, centers, st));
+  OSFM_HIP(in.upload(d_bearings, bearings, st));
+  return run_device(ctx, st, BearingRows{d_centers, d_bearings}, track_offsets, n_tracks, params, call, kernel_ms, who);
+}
+
+// an entry point over pixels: the checks, the tables and observations to the device, then both kernels of `call`
+template <class Call>
+int tracks_call(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model, const double *cam_params,
+                int n_cams, const int32_t *obs_shot, const double *obs_xy, const int64_t *track_offsets, int n_tracks,
+                const osfm_triangulate_params *params, const Call &call, double *kernel_ms, const char *who) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
+  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
+  OSFM_REQUIRE(n_shots >= 0 && n_cams >= 0, OSFM_E_INVALID, "%s: negative size", who);
+  if (n_tracks == 0) return OSFM_OK;
+  const int64_t n_obs = track_offsets[n_tracks];
+  OSFM_TRY(call.check(n_obs, who));
+  OSFM_CTX_LOCK(ctx);
+  PixelRows rows;
+  OsfmArena in;
+  OSFM_TRY(upload_pixel_rows(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, n_obs, in, &rows, who));
+  return run_device(ctx, ctx->stream, rows, track_offsets, n_tracks, params, call, kernel_ms, who);
 }
 
 }  // namespace
@@ -480,55 +519,19 @@ extern "C" void osfm_triangulate_params_default(osfm_triangulate_params *p) {
   p->pad = 0;
 }
 
-static int bearings_call(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
-                         const osfm_triangulate_params *params, const double *initial_or_null, double *points, uint8_t *status,
-                         int32_t *iterations_used, double *kernel_ms, const char *who) {
-  if (kernel_ms) *kernel_ms = 0.0;
-  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
-  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
-  if (n_tracks == 0) return OSFM_OK;
-  OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
-  const int64_t n_obs = track_offsets[n_tracks];
-  OSFM_REQUIRE(n_obs == 0 || (centers && bearings), OSFM_E_INVALID, "%s: null centers / bearings", who);
-  OSFM_CTX_LOCK(ctx);
-  OSFM_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  OsfmPoolBuf in;
-  const size_t bytes = ((size_t)n_obs * 24 + 255) / 256 * 256;
-  OSFM_HIP(in.alloc(ctx, 2 * bytes));
-  double *d_centers = (double *)in.p, *d_bearings = (double *)((char *)in.p + bytes);
-  if (n_obs) {
-    OSFM_HIP(hipMemcpyAsync(d_centers, centers, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
-    OSFM_HIP(hipMemcpyAsync(d_bearings, bearings, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
-  }
-  return run_device(ctx, st, BearingRows{d_centers, d_bearings}, track_offsets, n_tracks, params, initial_or_null, points, status, iterations_used, kernel_ms, who);
+extern "C" int osfm_triangulate_bearings(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
+                                         const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used,
+                                         double *kernel_ms) {
+  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, params, PlainCall{nullptr, points, status, iterations_used}, kernel_ms,
+                       "osfm_triangulate_bearings");
 }
 
 extern "C" int osfm_triangulate_tracks(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots, const int32_t *cam_model,
                                        const double *cam_params, int n_cams, const int32_t *obs_shot, const double *obs_xy,
                                        const int64_t *track_offsets, int n_tracks, const osfm_triangulate_params *params, double *points,
                                        uint8_t *status, int32_t *iterations_used, double *kernel_ms) {
-  const char *who = "osfm_triangulate_tracks";
-  if (kernel_ms) *kernel_ms = 0.0;
-  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
-  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
-  OSFM_REQUIRE(n_shots >= 0 && n_cams >= 0, OSFM_E_INVALID, "%s: negative size", who);
-  if (n_tracks == 0) return OSFM_OK;
-  OSFM_REQUIRE(points && status && iterations_used, OSFM_E_INVALID, "%s: null points / status / iterations_used", who);
-  const int64_t n_obs = track_offsets[n_tracks];
-  OSFM_CTX_LOCK(ctx);
-  PixelRows rows;
-  OsfmPoolBuf in;
-  OSFM_TRY(upload_pixel_rows(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, n_obs, in, &rows, who));
-  hipStream_t st = ctx->stream;
-  return run_device(ctx, st, rows, track_offsets, n_tracks, params, nullptr, points, status, iterations_used, kernel_ms, who);
-}
-
-extern "C" int osfm_triangulate_bearings(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
-                                         const osfm_triangulate_params *params, double *points, uint8_t *status, int32_t *iterations_used,
-                                         double *kernel_ms) {
-  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, params, nullptr, points, status, iterations_used, kernel_ms,
-                       "osfm_triangulate_bearings");
+  return tracks_call(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, track_offsets, n_tracks, params,
+                     PlainCall{nullptr, points, status, iterations_used}, kernel_ms, "osfm_triangulate_tracks");
 }
 
 extern "C" int osfm_triangulate_refine(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets, int n_tracks,
@@ -540,35 +543,16 @@ extern "C" int osfm_triangulate_refine(osfm_ctx *ctx, const double *centers, con
   p.refinement_iterations = refinement_iterations;
   OSFM_REQUIRE(n_tracks <= 0 || initial, OSFM_E_INVALID, "%s: null initial points", who);
   std::vector<uint8_t> status((size_t)(n_tracks > 0 ? n_tracks : 0));
-  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, &p, n_tracks > 0 ? initial : nullptr, points, status.data(),
-                       iterations_used, kernel_ms, who);
+  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, &p, PlainCall{n_tracks > 0 ? initial : nullptr, points, status.data(), iterations_used},
+                       kernel_ms, who);
 }
 
 extern "C" int osfm_triangulate_bearings_robust(osfm_ctx *ctx, const double *centers, const double *bearings, const int64_t *track_offsets,
                                                 int n_tracks, const osfm_triangulate_params *params, const double *draws, uint64_t seed,
                                                 double *points, uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers, int32_t *tries_used,
                                                 double *kernel_ms) {
-  const char *who = "osfm_triangulate_bearings_robust";
-  if (kernel_ms) *kernel_ms = 0.0;
-  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
-  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
-  if (n_tracks == 0) return OSFM_OK;
-  const int64_t n_obs = track_offsets[n_tracks];
-  const RobustResults res{points, status, inlier_mask, n_inliers, tries_used};
-  OSFM_TRY(check_robust_results(res, n_obs, who));
-  OSFM_REQUIRE(n_obs == 0 || (centers && bearings), OSFM_E_INVALID, "%s: null centers / bearings", who);
-  OSFM_CTX_LOCK(ctx);
-  OSFM_HIP(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  OsfmPoolBuf in;
-  const size_t bytes = ((size_t)n_obs * 24 + 255) / 256 * 256;
-  OSFM_HIP(in.alloc(ctx, 2 * bytes));
-  double *d_centers = (double *)in.p, *d_bearings = (double *)((char *)in.p + bytes);
-  if (n_obs) {
-    OSFM_HIP(hipMemcpyAsync(d_centers, centers, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
-    OSFM_HIP(hipMemcpyAsync(d_bearings, bearings, (size_t)n_obs * 24, hipMemcpyHostToDevice, st));
-  }
-  return run_device_robust(ctx, st, BearingRows{d_centers, d_bearings}, track_offsets, n_tracks, params, draws, seed, res, kernel_ms, who);
+  return bearings_call(ctx, centers, bearings, track_offsets, n_tracks, params,
+                       RobustCall{draws, seed, points, status, inlier_mask, n_inliers, tries_used}, kernel_ms, "osfm_triangulate_bearings_robust");
 }
 
 extern "C" int osfm_triangulate_tracks_robust(osfm_ctx *ctx, const double *shot_pose, const int32_t *shot_camera, int n_shots,
@@ -576,18 +560,6 @@ extern "C" int osfm_triangulate_tracks_robust(osfm_ctx *ctx, const double *shot_
                                               const double *obs_xy, const int64_t *track_offsets, int n_tracks,
                                               const osfm_triangulate_params *params, const double *draws, uint64_t seed, double *points,
                                               uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers, int32_t *tries_used, double *kernel_ms) {
-  const char *who = "osfm_triangulate_tracks_robust";
-  if (kernel_ms) *kernel_ms = 0.0;
-  OSFM_REQUIRE(ctx, OSFM_E_INVALID, "%s: null context", who);
-  OSFM_TRY(check_args(track_offsets, n_tracks, params, who));
-  OSFM_REQUIRE(n_shots >= 0 && n_cams >= 0, OSFM_E_INVALID, "%s: negative size", who);
-  if (n_tracks == 0) return OSFM_OK;
-  const int64_t n_obs = track_offsets[n_tracks];
-  const RobustResults res{points, status, inlier_mask, n_inliers, tries_used};
-  OSFM_TRY(check_robust_results(res, n_obs, who));
-  OSFM_CTX_LOCK(ctx);
-  PixelRows rows;
-  OsfmPoolBuf in;
-  OSFM_TRY(upload_pixel_rows(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, n_obs, in, &rows, who));
-  return run_device_robust(ctx, ctx->stream, rows, track_offsets, n_tracks, params, draws, seed, res, kernel_ms, who);
+  return tracks_call(ctx, shot_pose, shot_camera, n_shots, cam_model, cam_params, n_cams, obs_shot, obs_xy, track_offsets, n_tracks, params,
+                     RobustCall{draws, seed, points, status, inlier_mask, n_inliers, tries_used}, kernel_ms, "osfm_triangulate_tracks_robust");
 }

@@ -646,18 +646,13 @@ extern "C" int osfm_knn_points(osfm_ctx *ctx, const double *candidates, int n_ca
   OSFM_CTX_LOCK(ctx);
   OSFM_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  double *d_c = nullptr, *d_q = nullptr, *d_d = nullptr;
-  int32_t *d_i = nullptr;
-  struct Free {
-    void **p[4];
-    ~Free() {
-      for (auto q : p) (void)hipFree(*q);
-    }
-  } guard{{(void **)&d_c, (void **)&d_q, (void **)&d_d, (void **)&d_i}};
+  OsfmDevBuf b_c, b_q, b_d, b_i;
   const int nqp = (n_queries + 255) / 256 * 256;
-  OSFM_REQUIRE(dev_alloc(&d_c, (size_t)n_candidates * 3) == OSFM_OK && dev_alloc(&d_q, (size_t)n_queries * 3) == OSFM_OK &&
-                   dev_alloc(&d_d, (size_t)nqp * k) == OSFM_OK && dev_alloc(&d_i, (size_t)nqp * k) == OSFM_OK,
+  OSFM_REQUIRE(b_c.alloc((size_t)n_candidates * 3 * sizeof(double)) == hipSuccess && b_q.alloc((size_t)n_queries * 3 * sizeof(double)) == hipSuccess &&
+                   b_d.alloc((size_t)nqp * k * sizeof(double)) == hipSuccess && b_i.alloc((size_t)nqp * k * sizeof(int32_t)) == hipSuccess,
                OSFM_E_NOMEM, "osfm_knn_points: out of device memory");
+  double *d_c = b_c.as<double>(), *d_q = b_q.as<double>(), *d_d = b_d.as<double>();
+  int32_t *d_i = b_i.as<int32_t>();
   if (n_candidates > 0) OSFM_HIP(hipMemcpyAsync(d_c, candidates, (size_t)n_candidates * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   OSFM_HIP(hipMemcpyAsync(d_q, queries, (size_t)n_queries * 3 * sizeof(double), hipMemcpyHostToDevice, st));
   const double md2 = std::isfinite(max_distance) ? max_distance * max_distance : INFINITY;

@@ -14,7 +14,8 @@ CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 def build(force: bool = False) -> str:
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, "libosfm_cloud_emu.so")
-    deps = [os.path.join(CSRC, f) for f in ("cloud.hip", "ba_math.h", "osfm_internal.h")] + [os.path.join(HERE, "emu_ctx.cpp"), os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, "cloud.hip")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    deps += [os.path.join(HERE, "emu_ctx.cpp"), os.path.abspath(__file__)]
     deps += [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(HERE, "hipemu")) for f in fs]
     deps.append(os.path.join(ROOT, "include", "osfm_mi355.h"))
     if not force and os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps):

@@ -1,7 +1,8 @@
-"""Builds tests/native/_build/libosfm_triangulate_emu.so: the product's track triangulation (opensfm_amd/csrc/triangulate.hip, unmodified)
-compiled for the HOST against the HIP emulation of tests/native/hipemu, with the context plumbing of emu_ctx.cpp -- both kernels and the
-host side of the library then run on the CPU.  ``build_main()`` links the same two sources with tests/native/triangulate_main.cpp into a
-stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer.  TEST INFRASTRUCTURE: nothing under opensfm_amd/ loads either."""
+"""Builds tests/native/_build/libosfm_triangulate_emu.so: the product's track triangulation (opensfm_amd/csrc/triangulate.hip, unmodified,
+the plain and the robust kernels) compiled for the HOST against the HIP emulation of tests/native/hipemu, with the context plumbing of
+emu_ctx.cpp -- the kernels and the host side of the library then run on the CPU.  ``build_main(name)`` links the same two sources with
+tests/native/<name>.cpp (triangulate_main, triangulate_robust_main) into a stand-alone program under AddressSanitizer and
+UndefinedBehaviorSanitizer.  TEST INFRASTRUCTURE: nothing under opensfm_amd/ loads either."""
 import os
 import subprocess
 
@@ -16,8 +17,8 @@ SOURCES = ((os.path.join(CSRC, "triangulate.hip"), ["-x", "c++"]), (os.path.join
 
 
 def _deps():
-    deps = [os.path.join(CSRC, f) for f in ("triangulate.hip", "triangulate_core.h", "relpose_core.h", "osfm_internal.h")]
-    deps += [os.path.join(HERE, "emu_ctx.cpp"), os.path.abspath(__file__), os.path.join(ROOT, "include", "osfm_mi355.h")]
+    deps = [src for src, _ in SOURCES] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
+    deps += [os.path.abspath(__file__), os.path.join(ROOT, "include", "osfm_mi355.h")]
     return deps + [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(HERE, "hipemu")) for f in fs]
 
 
@@ -43,11 +44,11 @@ def build(force: bool = False) -> str:
     return so
 
 
-def build_main(force: bool = False) -> str:
-    """the stand-alone sanitised program (its own main; nothing of it is loaded into Python)"""
+def build_main(name: str = "triangulate_main", force: bool = False) -> str:
+    """the stand-alone sanitised program of tests/native/<name>.cpp (its own main; nothing of it is loaded into Python)"""
     os.makedirs(OUT, exist_ok=True)
-    exe = os.path.join(OUT, "triangulate_main_asan")
-    main = os.path.join(HERE, "triangulate_main.cpp")
+    exe = os.path.join(OUT, name + "_asan")
+    main = os.path.join(HERE, name + ".cpp")
     if not force and _fresh(exe, _deps() + [main]):
         return exe
     # (a fibre's whole stack shadow is cleared at every switch to it: small stacks keep the run short)
@@ -59,4 +60,5 @@ def build_main(force: bool = False) -> str:
 
 if __name__ == "__main__":
     print(build(force=True))
-    print(build_main(force=True))
+    print(build_main("triangulate_main", force=True))
+    print(build_main("triangulate_robust_main", force=True))

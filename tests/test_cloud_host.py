@@ -178,6 +178,14 @@ def test_emulated_edge_cases(emu):
         opensfm_adapter.points_isolation(bad)
     with pytest.raises(_lib.OsfmError, match=r"\(-1\)"):
         run_conditioning(dict(scene, obs_point=scene["obs_point"] + 1000))
+    shot_camera = np.array(scene["shot_camera"])
+    shot_camera[2] = len(scene["cam_model"])
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_points_conditioning: shot 2 names a camera outside the table") + "$"):
+        run_conditioning(dict(scene, shot_camera=shot_camera))
+    cam_model = np.array(scene["cam_model"])
+    cam_model[0] = 99
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_points_conditioning: camera 0 has model 99") + "$"):
+        run_conditioning(dict(scene, cam_model=cam_model))
 
 
 def test_far_points_reach_the_brute_force_kernel(emu):

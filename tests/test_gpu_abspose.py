@@ -3,6 +3,7 @@ header (tests/native/abspose_host.cpp) bit for bit; the pixels twin; compat.pyro
 against the reference tests' tolerances; reconstruction.resect / resect_candidates against a per-image loop over the host build on a
 synthetic map; the documented errors."""
 import copy
+import re
 
 import numpy as np
 import pytest
@@ -335,8 +336,8 @@ def test_documented_errors(gpu_ctx):
     for ic, cm, cp in ((np.zeros(1), [0], np.zeros((1, 16))), (np.zeros(2), [0, 0], np.zeros((1, 16))), (np.zeros(2), [0], np.zeros((1, 9)))):
         with pytest.raises(ValueError):  # image_cam / camera table of the wrong shape: refused before the call
             reconstruction.abspose_images_pixels(xy, b, [0, 5, 10], ic, cm, cp, THRESHOLD, ctx=gpu_ctx)
-    for ic in ([0, 1], [-1, 0]):  # a camera index outside the table
-        with pytest.raises(OsfmError, match="outside the table"):
+    for ic, image in (([0, 1], 1), ([-1, 0], 0)):  # a camera index outside the table
+        with pytest.raises(OsfmError, match=re.escape("(-1): osfm_abspose_images_pixels: image %d names a camera outside the table" % image) + "$"):
             reconstruction.abspose_images_pixels(xy, b, [0, 5, 10], np.array(ic), [0], np.zeros((1, 16)), THRESHOLD, ctx=gpu_ctx)
     with pytest.raises(OsfmError, match="at least 3"):
         pygeometry.absolute_pose_n_points(b[:2], b[:2])

@@ -3,6 +3,8 @@ build of the same header (tests/native/relrot_host.cpp) bit for bit; the documen
 against the reference test's tolerances; opensfm_amd.reconstruction.compute_image_pairs against the host restatement of the
 reference's flow on a fake DataSet with four camera models."""
 
+import re
+
 import numpy as np
 import pytest
 
@@ -90,6 +92,11 @@ def test_documented_errors(gpu_ctx):
                        (np.zeros((2, 2)), [0], np.zeros((1, 9)))):  # pair_cams / camera table of the wrong shape: refused before the call
         with pytest.raises(ValueError):
             reconstruction.relrot_pairs_pixels(px, px, [0, 5, 10], pc, cm, cp, 0.016, ctx=gpu_ctx)
+    # one pair of 3 correspondences with a bad camera table: refused before any kernel is launched
+    with pytest.raises(OsfmError, match=re.escape("(-1): osfm_relrot_pairs_pixels: camera 0 has model 99") + "$"):
+        reconstruction.relrot_pairs_pixels(px[:3], px[:3], [0, 3], np.array([[0, 0]]), [99], np.zeros((1, 16)), 0.016, ctx=gpu_ctx)
+    with pytest.raises(OsfmError, match=re.escape("(-1): osfm_relrot_pairs_pixels: pair 0 names a camera outside the table") + "$"):
+        reconstruction.relrot_pairs_pixels(px[:3], px[:3], [0, 3], np.array([[0, -1]]), [0], np.zeros((1, 16)), 0.016, ctx=gpu_ctx)
     prm = pyrobust.RobustEstimatorParams()
     with pytest.raises(NotImplementedError):
         pyrobust.ransac_relative_rotation(b, b, 0.01, prm, pyrobust.MSAC)

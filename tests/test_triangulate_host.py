@@ -6,6 +6,7 @@ import contextlib
 import ctypes as C
 import importlib.util
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -180,10 +181,20 @@ def test_emulated_edge_cases(emu):
             tracks(obs_shot=obs_shot)
     shot_camera = scene["shot_camera"].copy()
     shot_camera[3] = 2
-    with pytest.raises(_lib.OsfmError, match=invalid):
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_triangulate_tracks: shot 3 names a camera outside the table") + "$"):
         tracks(shot_camera=shot_camera)
-    with pytest.raises(_lib.OsfmError, match=invalid):
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_triangulate_tracks: camera 1 has model 10") + "$"):
         tracks(cam_model=np.array([0, 10], np.int32))
+
+    def robust_tracks(**changes):
+        s = dict(scene, **changes)
+        return reconstruction.triangulate_tracks_arrays_robust(s["shot_pose"], s["shot_camera"], s["cam_model"], s["cam_params"], s["obs_shot"],
+                                                               s["obs_xy"], s["offsets"], seed=1)
+
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_triangulate_tracks_robust: shot 3 names a camera outside the table") + "$"):
+        robust_tracks(shot_camera=shot_camera)
+    with pytest.raises(_lib.OsfmError, match=re.escape("(-1): osfm_triangulate_tracks_robust: camera 1 has model 10") + "$"):
+        robust_tracks(cam_model=np.array([0, 10], np.int32))
     for value in (np.nan, np.inf):
         obs_xy = scene["obs_xy"].copy()
         obs_xy[-1, 1] = value  # in the 300-observation track: the wavefront kernel finds it

@@ -1,5 +1,5 @@
 """The robust track triangulation of ``opensfm_amd/csrc/triangulate.hip`` (``triangulation_type: ROBUST``) without a GPU: the kernels on the
-host emulation of HIP (``tests/native/build_triangulate_robust_emu.py``) against the step-by-step restatement of
+host emulation of HIP (``tests/native/build_triangulate_emu.py``) against the step-by-step restatement of
 ``tests/triangulate_robust_cases.py``, the restatement against the reference's own ``TrackTriangulator.triangulate_robust`` (where the
 reference is mounted), the unranking and the generator of ``triangulate_robust.h`` against ``itertools.combinations`` and Python integers,
 the keyworded Python drop-ins against a per-track loop, and a stand-alone sanitised program over the rays scene."""
@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _builder():
-    spec = importlib.util.spec_from_file_location("build_triangulate_robust_emu", os.path.join(HERE, "native", "build_triangulate_robust_emu.py"))
+    spec = importlib.util.spec_from_file_location("build_triangulate_emu", os.path.join(HERE, "native", "build_triangulate_emu.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
@@ -55,7 +55,7 @@ def emu():
 @pytest.fixture(scope="module")
 def program():
     """the stand-alone program (sanitised; its own main)"""
-    return _builder().build_main()
+    return _builder().build_main("triangulate_robust_main")
 
 
 def run_program(exe, args, text=None):
