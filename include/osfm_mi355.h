@@ -769,6 +769,82 @@ int osfm_triangulate_tracks_robust(osfm_ctx *ctx, const double *shot_pose, const
                                    uint64_t seed, double *points, uint8_t *status, uint8_t *inlier_mask, int32_t *n_inliers,
                                    int32_t *tries_used, double *kernel_ms);
 
+/* =====================================================================================
+ * Depthmaps (opensfm/src/dense/src/depthmap.cc: dense::DepthmapEstimator and dense::DepthmapCleaner), depthmap.hip + depthmap_core.h:
+ * what dense.compute_depthmap and dense.clean_depthmap do shot by shot, for a batch of shots in one call.
+ *
+ * OpenCV is not available to this project, so depthmap.cc is RESTATED, quirks included: float32 where it uses float, double where it
+ * uses double, its order of operations, no contraction.  Per candidate plane v and other view o:  H = K_o (Q_o + a_o v^T) K_0^-1 in
+ * double (Q_o = R_o R_0^T, a_o = Q_o t_0 - t_o, every product summed k = 0, 1, 2), narrowed to float; u, v, w, the four derivatives and
+ * the sample coordinates of lines 433-459; LinearInterpolation is 0 outside [0, cols - 1) x [0, rows - 1); the six NCC sums accumulate
+ * in float, dy then dx; the score is -1 when the weights sum to 0 or a variance is below 0.1; over the views a strict > keeps the lowest
+ * view index on a tie.  BRUTE_FORCE: plane d has the depth of lines 193-198 and the normal (0, 0, -1); a candidate is accepted only if
+ * its score exceeds the current one, starting from 0, so a pixel whose NCC is never positive stays all-zero.  PATCH_MATCH and
+ * PATCH_MATCH_SAMPLE: RandomInitialization, ComputeIgnoreMask (mask == 0, or the population variance of the patch, in float, below
+ * min_patch_sd^2), patchmatch_iterations forward and backward raster sweeps -- two adjacent-plane candidates, six perturbations with
+ * the ranges 0.02 * 0.3^k and 0.5 * 0.8^k, in sample mode with more than two views one other-neighbour candidate, each using the current
+ * values -- and PostProcess (5 x 5 median, depth zeroed where depth == 0 or |d - m| / d > 0.05).  The sweeps run as diagonal
+ * wavefronts, which reproduce the sequential raster order exactly.  DepthmapCleaner::Clean is lines 515-541: the backprojected point and
+ * the reprojection narrowed to float, the z_epsilon and NaN tests, |depth_at - depth_of| < depth_of * same_depth_threshold.
+ * From memory of OpenCV, NOT compared with its source: the 3 x 3 inverse (cofactors times the reciprocal determinant), Vec3f / float as a
+ * product with 1.f / alpha, and cv::medianBlur's replicated border.  Whether the unqualified exp() (lines 344, 473) and fabs() (line 485) resolve to the float or
+ * the double overload is not pinned either; a refused call has touched none of the caller's outputs.
+ * Divergences:
+ *   - a sample coordinate that is NaN reads as 0 (the reference casts it to int: undefined);
+ *   - the bilateral weight: its argument in float as at line 473, exp() in double on the host, rounded to float, tabulated by |dcolor|
+ *     (0 .. 255) and dx^2 + dy^2 (0 .. 98) -- within one float ulp of the reference's expf;
+ *   - randomness (the reference draws from rand() and a random_device-seeded mt19937: two of its own runs differ).  Draw k of pixel
+ *     `pixel` = row * width + column in sweep s (0 the initialisation, 1 + 2 it / 2 + 2 it the forward / backward pass of iteration it) is,
+ *     in uint64 arithmetic,  z = seed + 0x9E3779B97F4A7C15 * (((s << 40) + pixel) * 32 + k + 1), then splitmix64's finaliser (as for
+ *     robust triangulation).  Initialisation: k = 0 depth = init_depth[z >> 52], k = 1, 2 normal x, y = (float)(z >> 40) * 2^-23 - 1,
+ *     k = 3 neighbour = 1 + (uint32)(z >> 32) mod (N - 1).  A sweep: perturbation q uses k = 3 q for the depth factor
+ *     factor[q][z >> 52] and k = 3 q + 1, 3 q + 2 for normal[z >> 52]; k = 18 is the other neighbour
+ *     1 + (current + (uint32)(z >> 32) mod (N - 2)) mod (N - 1)  (an offset instead of the reference's redraw loop).  The tables are
+ *     built on the host in double: normal[m] = Phi^-1((m + 1/2) / 4096), factor[q][m] = exp(depth_range_q * normal[m]),
+ *     init_depth[m] = exp(log min + (log max - log min) (m + 1/2) / 4096).  Same distributions, discretised; another mechanism;
+ *   - an even patch_size (the reference's Variance then reads stale buffer entries) and patch_size 1 (its sweep reads outside the image)
+ *     are refused; with a single view no candidate is ever scored in a view: both PatchMatch modes keep the initial score -1 and
+ *     nghbr 0 (the reference's sample mode scores view 0 against itself), brute force stays all-zero as in the reference.
+ * A batch: problem b owns the views view_offsets[b] .. view_offsets[b + 1] (at most 32; none: nothing is written), the first being the
+ * shot itself.  K, R (row-major 3 x 3) and t per view; images / masks / depths are per-view pointers to row-major height x width
+ * arrays (only the mask of a problem's first view is read); views may differ in size.  Outputs are per-problem pointers to the shot's
+ * height x width arrays: depth, plane (x 3), score float32 and nghbr int32.  An image smaller than the patch gives zeros without a
+ * launch.  OSFM_E_INVALID: an even patch_size, one below 3 or above 15, more than 32 views, a K, R or t that is not finite,
+ * min_depth <= 0 or max_depth < min_depth (estimate), num_depth_planes < 1.  A batch gives byte for byte what single calls give, and
+ * two runs are byte-equal.  kernel_ms may be NULL.
+ * osfm_depthmap_tables copies the tables the library uses: normal (4096), factor (6 x 4096), weight (256 x 99) and, for a depth range,
+ * init_depth (4096); any pointer may be NULL.
+ * ===================================================================================== */
+#define OSFM_DEPTHMAP_BRUTE_FORCE 0
+#define OSFM_DEPTHMAP_PATCH_MATCH 1
+#define OSFM_DEPTHMAP_PATCH_MATCH_SAMPLE 2
+typedef struct osfm_depthmap_params { /* opensfm/config.py:346-368 */
+  double min_depth;             /* depthmap_min_depth: 0 = inferred by the caller */
+  double max_depth;             /* depthmap_max_depth */
+  double min_patch_sd;          /* depthmap_min_patch_sd */
+  double min_correlation_score; /* depthmap_min_correlation_score (applied by the Python layer, as dense.compute_depthmap does) */
+  double same_depth_threshold;  /* depthmap_same_depth_threshold */
+  int32_t method;               /* depthmap_method: OSFM_DEPTHMAP_* */
+  int32_t resolution;           /* depthmap_resolution */
+  int32_t num_neighbors;        /* depthmap_num_neighbors */
+  int32_t num_matching_views;   /* depthmap_num_matching_views */
+  int32_t patchmatch_iterations;
+  int32_t patch_size;
+  int32_t min_consistent_views;
+  int32_t num_depth_planes;     /* 100: what dense.compute_depthmap passes to set_depth_range */
+  int32_t pad;
+} osfm_depthmap_params;
+
+void osfm_depthmap_params_default(osfm_depthmap_params *p);
+int osfm_depthmap_tables(double min_depth, double max_depth, float *normal, float *factor, float *weight, float *init_depth);
+int osfm_depthmap_estimate(osfm_ctx *ctx, int n_problems, const int32_t *view_offsets, const double *K, const double *R, const double *t,
+                           const uint8_t *const *images, const uint8_t *const *masks, const int32_t *widths, const int32_t *heights,
+                           const double *min_depth, const double *max_depth, const osfm_depthmap_params *params, uint64_t seed,
+                           float *const *depth, float *const *plane, float *const *score, int32_t *const *nghbr, double *kernel_ms);
+int osfm_depthmap_clean(osfm_ctx *ctx, int n_problems, const int32_t *view_offsets, const double *K, const double *R, const double *t,
+                        const float *const *depths, const int32_t *widths, const int32_t *heights, const osfm_depthmap_params *params,
+                        float *const *clean, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,25 @@ class TriangulateParams(C.Structure):
     ]
 
 
+class DepthmapParams(C.Structure):
+    _fields_ = [
+        ("min_depth", C.c_double),
+        ("max_depth", C.c_double),
+        ("min_patch_sd", C.c_double),
+        ("min_correlation_score", C.c_double),
+        ("same_depth_threshold", C.c_double),
+        ("method", C.c_int32),
+        ("resolution", C.c_int32),
+        ("num_neighbors", C.c_int32),
+        ("num_matching_views", C.c_int32),
+        ("patchmatch_iterations", C.c_int32),
+        ("patch_size", C.c_int32),
+        ("min_consistent_views", C.c_int32),
+        ("num_depth_planes", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class RelposeResult(C.Structure):
     _fields_ = [
         ("model", C.c_double * 12),
@@ -242,6 +261,21 @@ SIGNATURES = {
          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(TriangulateParams), C.POINTER(C.c_double),
          C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
          C.POINTER(C.c_double)],
+    ),
+    "osfm_depthmap_params_default": (None, [C.POINTER(DepthmapParams)]),
+    "osfm_depthmap_tables": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float)]),
+    "osfm_depthmap_estimate": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.POINTER(DepthmapParams), C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_double)],
+    ),
+    "osfm_depthmap_clean": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(DepthmapParams), C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
     ),
     "osfm_match_guided": (
         C.c_int,

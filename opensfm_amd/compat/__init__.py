@@ -5,15 +5,19 @@ The reference imports its extensions as ``from opensfm import pyfeatures`` ...; 
 puts these modules in front: ``opensfm_amd.compat.install()`` registers them in ``sys.modules`` as ``opensfm.pyfeatures`` etc. for every
 name that is NOT already importable (it never shadows a compiled extension unless ``force=True``), attribute by attribute: an attribute
 this package does not provide is looked up in the compiled module when there is one, and raises ``AttributeError`` naming the missing
-entry otherwise -- there is no CPU fallback behind these names."""
+entry otherwise -- there is no CPU fallback behind these names.
+
+``pydense`` (``DepthmapEstimator``, ``DepthmapCleaner``) is registered on request only: ``install(..., extra=("pydense",))`` or
+``install_dense()``; what ``install()`` registers by default does not change."""
 import importlib
 import sys
 import types
-from typing import Dict
+from typing import Dict, Sequence
 
-from . import pybundle, pyfeatures, pyrobust, pysfm
+from . import pybundle, pydense, pyfeatures, pyrobust, pysfm
 
 MODULES = {"pyfeatures": pyfeatures, "pyrobust": pyrobust, "pybundle": pybundle, "pysfm": pysfm}
+EXTRA_MODULES = {"pydense": pydense}  # registered only when asked for
 
 
 class _Overlay(types.ModuleType):
@@ -30,10 +34,16 @@ class _Overlay(types.ModuleType):
         raise AttributeError(f"{self.__name__}.{attr} is not provided by opensfm_amd.compat (GPU hot-path subset) and no compiled module is present")
 
 
-def install(package: str = "opensfm", force: bool = False) -> Dict[str, types.ModuleType]:
-    """register ``<package>.pyfeatures`` ... in ``sys.modules``; returns what was registered"""
+def install(package: str = "opensfm", force: bool = False, extra: Sequence[str] = ()) -> Dict[str, types.ModuleType]:
+    """register ``<package>.pyfeatures`` ... in ``sys.modules``, and the modules of EXTRA_MODULES named in `extra`; returns what was
+    registered"""
     done = {}
-    for name, gpu in MODULES.items():
+    wanted = dict(MODULES)
+    for name in extra:
+        if name not in EXTRA_MODULES:
+            raise ValueError(f"opensfm_amd.compat has no optional module {name!r} (there is: {sorted(EXTRA_MODULES)})")
+        wanted[name] = EXTRA_MODULES[name]
+    for name, gpu in wanted.items():
         full = f"{package}.{name}"
         compiled = None
         try:
@@ -51,3 +61,8 @@ def install(package: str = "opensfm", force: bool = False) -> Dict[str, types.Mo
         if pkg is not None:
             setattr(pkg, name, done[name])
     return done
+
+
+def install_dense(package: str = "opensfm", force: bool = False) -> Dict[str, types.ModuleType]:
+    """``install(package, force, extra=("pydense",))``: the default modules and ``<package>.pydense``"""
+    return install(package, force, extra=("pydense",))
