@@ -845,6 +845,64 @@ int osfm_depthmap_clean(osfm_ctx *ctx, int n_problems, const int32_t *view_offse
                         const float *const *depths, const int32_t *widths, const int32_t *heights, const osfm_depthmap_params *params,
                         float *const *clean, double *kernel_ms);
 
+/* =====================================================================================
+ * Image undistortion (opensfm/undistort.py: undistort_image, scale_image, render_perspective_view_of_a_panorama), a batch per call.
+ *
+ * osfm_camera_mapping is pygeometry.compute_camera_mapping (geometry/src/camera.cc:319-342) literally, in double, without contraction:
+ * n = max(width, height), uv = (u - width 0.5, v - height 0.5), p = n from.Project(to.Bearing((1 / n) uv)),
+ * map1[v][u] = (float)(p0 + width 0.5), map2[v][u] = (float)(p1 + height 0.5); the bearing is the normalised one of osfm_pixel_bearings.
+ * Entry i has its own (from, to, width, height): cameras as model id + 16 doubles in the native order.  map1[i] / map2[i] point to
+ * height x width floats.  osfm_panorama_mapping is the map of render_perspective_view_of_a_panorama: destination pixel (float32) ->
+ * normalized_image_coordinates (float32 arithmetic, as numpy does there) -> the bearing of the view camera `to` -> rotations[i]
+ * (R_pano R_view^T, row-major 3 x 3) -> from.Project -> denormalized_image_coordinates for a src_w x src_h panorama, narrowed to float.
+ *
+ * OpenCV is not available to this project, so cv2.remap and cv2.resize are RESTATED from memory of OpenCV, unpinned:
+ *   - OSFM_INTER_LINEAR on uint8 (OSFM_INTER_AREA is treated as OSFM_INTER_LINEAR, as cv2.remap does): sx = round_half_even(x 32),
+ *     integer part sx >> 5 (arithmetic shift: floor), fraction fx = sx & 31, the same for y; the four taps get the int32 weights
+ *     32 (32 - fx)(32 - fy), 32 fx (32 - fy), 32 (32 - fx) fy, 32 fx fy (their sum is 32768); out = (sum tap weight + 16384) >> 15,
+ *     per channel with the same weights;
+ *   - OSFM_INTER_NEAREST: the tap (round_half_even(x), round_half_even(y));
+ *   - OSFM_BORDER_CONSTANT: a tap outside the image reads 0;  OSFM_BORDER_WRAP: a tap index is taken modulo the size in both axes, with a
+ *     non-negative result;
+ *   - out_w == map_w and out_h == map_h: no scaling.  Anything else is scale_image's cv2.resize(INTER_NEAREST) of the full-size remap:
+ *     output pixel X reads the map at src_x = min(floor(X (1.0 / ((double)out_w / map_w))), map_w - 1), the same in y, and only those
+ *     pixels are computed -- byte for byte what full-size remap followed by nearest resize gives.  The output size itself
+ *     (int(round(w factor)) with Python's round) is the caller's.
+ * Divergences:
+ *   - a map entry that is NaN or infinite, or whose rounded fixed-point value does not fit int32, gives 0 in either border mode
+ *     (OpenCV's cast is undefined there);
+ *   - an image, map or output side above 32767 is refused (OpenCV's int16 maps cannot address it either);
+ *   - only uint8 with 1, 3 or 4 interleaved channels; uint16 ("anydepth") images are refused by the Python layer with the code of
+ *     OSFM_E_INVALID and a message naming the dtype, never converted.
+ * osfm_remap_images: image i (src_w x src_h x channels) through map1[i] / map2[i] (map_w x map_h; images may share a map: it is uploaded
+ * once) into dst[i] (out_w x out_h x channels).  osfm_undistort_images is the fused path for frame cameras: image i uses the pair
+ * (from, to) number image_cam[i] of a table of n_cams pairs; the map entry is computed in registers by the function osfm_camera_mapping
+ * uses and narrowed to float, so the bytes equal osfm_remap_images on osfm_camera_mapping's output; border OSFM_BORDER_CONSTANT.
+ * A batch of zero is a no-op that succeeds; a batch holds at most 65535 entries.  OSFM_E_INVALID: channels not 1, 3 or 4, a non-positive
+ * size, a side above 32767, a camera parameter (or rotation entry) that is not finite, an unknown model, interpolation or border value,
+ * an image_cam index out of range; a refused call has touched none of the caller's outputs.  A batch gives byte for byte what single
+ * calls give, and two runs are byte-equal.  kernel_ms may be NULL; it is written by calls that succeed (0 for an empty batch).
+ * ===================================================================================== */
+#define OSFM_INTER_NEAREST 0 /* cv2.INTER_NEAREST */
+#define OSFM_INTER_LINEAR 1  /* cv2.INTER_LINEAR */
+#define OSFM_INTER_AREA 3    /* cv2.INTER_AREA */
+#define OSFM_BORDER_CONSTANT 0 /* cv2.BORDER_CONSTANT */
+#define OSFM_BORDER_WRAP 3     /* cv2.BORDER_WRAP */
+int osfm_camera_mapping(osfm_ctx *ctx, int n_maps, const int32_t *from_model, const double *from_params, const int32_t *to_model,
+                        const double *to_params, const int32_t *widths, const int32_t *heights, float *const *map1, float *const *map2,
+                        double *kernel_ms);
+int osfm_panorama_mapping(osfm_ctx *ctx, int n_maps, const int32_t *from_model, const double *from_params, const int32_t *to_model,
+                          const double *to_params, const double *rotations, const int32_t *src_w, const int32_t *src_h,
+                          const int32_t *widths, const int32_t *heights, float *const *map1, float *const *map2, double *kernel_ms);
+int osfm_remap_images(osfm_ctx *ctx, int n_images, const uint8_t *const *src, const int32_t *src_w, const int32_t *src_h,
+                      const int32_t *channels, const float *const *map1, const float *const *map2, const int32_t *map_w,
+                      const int32_t *map_h, const int32_t *out_w, const int32_t *out_h, int interpolation, int border, uint8_t *const *dst,
+                      double *kernel_ms);
+int osfm_undistort_images(osfm_ctx *ctx, int n_images, const uint8_t *const *src, const int32_t *widths, const int32_t *heights,
+                          const int32_t *channels, const int32_t *image_cam, int n_cams, const int32_t *from_model, const double *from_params,
+                          const int32_t *to_model, const double *to_params, const int32_t *out_w, const int32_t *out_h, int interpolation,
+                          uint8_t *const *dst, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,29 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(DepthmapParams), C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
     ),
+    "osfm_camera_mapping": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+         C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
+    ),
+    "osfm_panorama_mapping": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_double)],
+    ),
+    "osfm_remap_images": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int,
+         C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
+    ),
+    "osfm_undistort_images": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+         C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
+    ),
     "osfm_match_guided": (
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_float),

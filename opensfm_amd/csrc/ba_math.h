@@ -62,7 +62,9 @@ static __device__ void rot_and_derivs(const double *r, double *R, double *dR /*[
 
 // PROJ stage of the camera (camera_projections_functions.h): PerspectiveProjection (:88-117) or
 // FisheyeProjection (:9-85: theta / r * (x, y), theta = atan2(r, z); perspective below r = 1e-8).
-template <bool JAC>
+// DIVIDE: u = x / z as the reference's Forward writes it (image undistortion repeats its bits); the solvers multiply by 1 / z, which
+// their Jacobians share.
+template <bool JAC, bool DIVIDE = false>
 __device__ __forceinline__ void project_stage(int model, const double *Xc, double &u, double &v, double *jp) {
   const double x = Xc[0], y = Xc[1], z = Xc[2];
   const double r2 = x * x + y * y, r = sqrt(r2);
@@ -83,8 +85,8 @@ __device__ __forceinline__ void project_stage(int model, const double *Xc, doubl
     return;
   }
   const double iz = 1.0 / z;
-  u = x * iz;
-  v = y * iz;
+  u = DIVIDE ? x / z : x * iz;
+  v = DIVIDE ? y / z : y * iz;
   if (JAC) {
     jp[0] = iz; jp[1] = 0.0; jp[2] = -x * iz * iz;
     jp[3] = 0.0; jp[4] = iz; jp[5] = -y * iz * iz;
@@ -149,8 +151,9 @@ static __device__ void distort_d2(int kind, const double *k, D2 x, D2 y, D2 &ox,
   oy = y * rad + ty;
 }
 
-// projection of a camera-frame point by a constant camera of model >= 2: out (2), J (2x3 w.r.t. Xc)
-template <bool JAC>
+// projection of a camera-frame point by a constant camera of any 2-D model (the solvers call it for models >= 2, image undistortion
+// for all nine): out (2), J (2x3 w.r.t. Xc)
+template <bool JAC, bool DIVIDE = false>
 __device__ void project_generic(int model, const double *par, const double *Xc, double *out, double *J) {
   int proj, kind, nd, na;
   model_layout(model, proj, kind, nd, na);
@@ -158,14 +161,14 @@ __device__ void project_generic(int model, const double *par, const double *Xc, 
   double u, v, jp[6];
   if (proj == 2) {  // DualProjection: t * perspective + (1 - t) * fisheye (camera_projections_functions.h:122-134)
     double ua, va, ja[6], ub, vb, jb[6];
-    project_stage<true>(OSFM_CAMERA_PERSPECTIVE, Xc, ua, va, ja);
-    project_stage<true>(OSFM_CAMERA_FISHEYE, Xc, ub, vb, jb);
+    project_stage<true, DIVIDE>(OSFM_CAMERA_PERSPECTIVE, Xc, ua, va, ja);
+    project_stage<true, DIVIDE>(OSFM_CAMERA_FISHEYE, Xc, ub, vb, jb);
     const double t = par[0];
     u = t * ua + (1.0 - t) * ub;
     v = t * va + (1.0 - t) * vb;
     for (int i = 0; i < 6; i++) jp[i] = t * ja[i] + (1.0 - t) * jb[i];
   } else {
-    project_stage<true>(proj, Xc, u, v, jp);
+    project_stage<true, DIVIDE>(proj, Xc, u, v, jp);
   }
   D2 dx, dy;
   distort_d2(kind, kd, D2{u, 1.0, 0.0}, D2{v, 0.0, 1.0}, dx, dy);
