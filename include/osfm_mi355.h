@@ -845,6 +845,44 @@ int osfm_depthmap_clean(osfm_ctx *ctx, int n_problems, const int32_t *view_offse
                         const float *const *depths, const int32_t *widths, const int32_t *heights, const osfm_depthmap_params *params,
                         float *const *clean, double *kernel_ms);
 
+/* -------------------------------------------------------------------------------------
+ * Pruning and merging (dense::DepthmapPruner::Prune, depthmap.cc:565-625), prune.hip + prune_core.h: what dense.prune_depthmap does
+ * shot by shot and dense.merge_depthmaps concatenates, for a batch of shots in one call.  The pruner does not stay on the host: its
+ * raster-ordered push_back is a prefix sum over per-pixel keep flags.
+ *
+ * RESTATED like the cleaner, with the pruner's own types.  Pixel (i, j) of a problem's first view: depth <= 0 skips it (a NaN depth
+ * does not: the pixel then meets only skipped views and is kept with a NaN point); normal = cv::normalize(plane);
+ * area = (float)((double)(-normal_z / depth) * K0(0,0)); point = Backproject in double narrowed to float.  Per other view the point is
+ * widened and projected in DOUBLE; the view is skipped when z < 1e-8 or z is NaN; iu = (int64)(x / z + 0.5), iv likewise -- truncation
+ * toward zero, so a value in (-1, 0) lands on column or row 0 and counts as inside; outside the image the view is skipped;
+ * depth_at = depths[other](iv, iu); when depth_at > (double)(1.f - (float)same_depth_threshold) * z the pixel is rejected if
+ * depth_at == 0 (reachable with a threshold of 1 or more) or if (double)(-normalize(planes[other](iv, iu))_z / depth_at) * Ko(0,0) > area.
+ * A kept pixel gives one row: the point, Rinv * normal (Rinv = R0 transposed, narrowed to float; float products summed k = 0, 1, 2),
+ * the colour and the label of view 0.
+ * From memory of OpenCV, NOT compared with its source: cv::normalize(Vec3f) as nv = sqrt of the squares summed in double, k = 0, 1, 2,
+ * then v * (nv ? 1. / nv : 0.) with each product formed in double and rounded to float; the order of the Matx33f * Vec3f sums.
+ * Divergences, both in place of undefined or implementation-defined behaviour:
+ *   1. x / z + 0.5 (or y / z + 0.5) that is NaN, infinite or 2^31 or more in magnitude counts as outside the image (the reference casts
+ *      it to int64: undefined);
+ *   2. the reference passes that int64 to IsInsideImage(..., int, int), an implementation-defined narrowing: the same values count as
+ *      outside here.
+ * The batch is laid out as for osfm_depthmap_clean; depths[v] is height x width float32, planes[v] height x width x 3 float32; colors[v]
+ * (height x width x 3) and labels[v] (height x width) are read, and uploaded, for the FIRST view of a problem only and may be NULL for
+ * the others.  The outputs are the merged cloud of the batch: the rows of problem 0 in raster order, then those of problem 1, ...;
+ * counts[b] (n_problems entries) gives the split.  A problem with no views or an empty first view has no rows.  `capacity` is the number
+ * of rows points (x 3), normals (x 3), out_colors (x 3) and out_labels hold: a batch that keeps more fails with OSFM_E_INVALID, counts
+ * filled in and the four outputs untouched (the number of first-view pixels with depth > 0 or NaN is always enough).  OSFM_E_INVALID
+ * also: a NaN same_depth_threshold, more than 32 views, a K, R or t that is not finite.  Zero problems: OSFM_OK, nothing launched.
+ * No atomic decides a row's place: a batch gives byte for byte what its single calls give, and two runs are byte-equal.  kernel_ms (may
+ * be NULL) is the sum of the three kernels; osfm_depthmap_prune_split_ms gives ms[3] = mark, scan, scatter of the context's last call
+ * that launched them.
+ * ------------------------------------------------------------------------------------- */
+int osfm_depthmap_prune(osfm_ctx *ctx, int n_problems, const int32_t *view_offsets, const double *K, const double *R, const double *t,
+                        const float *const *depths, const float *const *planes, const uint8_t *const *colors, const uint8_t *const *labels,
+                        const int32_t *widths, const int32_t *heights, const osfm_depthmap_params *params, int64_t capacity, float *points,
+                        float *normals, uint8_t *out_colors, uint8_t *out_labels, int64_t *counts /* n_problems */, double *kernel_ms);
+int osfm_depthmap_prune_split_ms(osfm_ctx *ctx, double *ms /* 3 */);
+
 /* =====================================================================================
  * Image undistortion (opensfm/undistort.py: undistort_image, scale_image, render_perspective_view_of_a_panorama), a batch per call.
  *

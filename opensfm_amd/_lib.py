@@ -277,6 +277,14 @@ SIGNATURES = {
         [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(DepthmapParams), C.POINTER(C.c_void_p), C.POINTER(C.c_double)],
     ),
+    "osfm_depthmap_prune": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_void_p),
+         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(DepthmapParams), C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+         C.POINTER(C.c_int64), C.POINTER(C.c_double)],
+    ),
+    "osfm_depthmap_prune_split_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "osfm_camera_mapping": (
         C.c_int,
         [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),

@@ -8,16 +8,19 @@ this package does not provide is looked up in the compiled module when there is 
 entry otherwise -- there is no CPU fallback behind these names.
 
 ``pydense`` (``DepthmapEstimator``, ``DepthmapCleaner``) is registered on request only: ``install(..., extra=("pydense",))`` or
-``install_dense()``; what ``install()`` registers by default does not change."""
+``install_dense()``; what ``install()`` registers by default does not change.  ``pydense_full`` is ``pydense`` plus ``DepthmapPruner``:
+``install(..., extra=("pydense_full",))`` or ``install_dense_full()`` registers it AS ``<package>.pydense`` (asking for both is a
+``ValueError``)."""
 import importlib
 import sys
 import types
 from typing import Dict, Sequence
 
-from . import pybundle, pydense, pyfeatures, pyrobust, pysfm
+from . import pybundle, pydense, pydense_full, pyfeatures, pyrobust, pysfm
 
 MODULES = {"pyfeatures": pyfeatures, "pyrobust": pyrobust, "pybundle": pybundle, "pysfm": pysfm}
-EXTRA_MODULES = {"pydense": pydense}  # registered only when asked for
+EXTRA_MODULES = {"pydense": pydense, "pydense_full": pydense_full}  # registered only when asked for
+REGISTERED_AS = {"pydense_full": "pydense"}  # an optional module that goes under another's name
 
 
 class _Overlay(types.ModuleType):
@@ -36,13 +39,16 @@ class _Overlay(types.ModuleType):
 
 def install(package: str = "opensfm", force: bool = False, extra: Sequence[str] = ()) -> Dict[str, types.ModuleType]:
     """register ``<package>.pyfeatures`` ... in ``sys.modules``, and the modules of EXTRA_MODULES named in `extra`; returns what was
-    registered"""
+    registered, by the name it was registered under (``pydense_full`` goes under ``pydense``)"""
     done = {}
     wanted = dict(MODULES)
     for name in extra:
         if name not in EXTRA_MODULES:
             raise ValueError(f"opensfm_amd.compat has no optional module {name!r} (there is: {sorted(EXTRA_MODULES)})")
-        wanted[name] = EXTRA_MODULES[name]
+        target = REGISTERED_AS.get(name, name)
+        if target in wanted and wanted[target] is not EXTRA_MODULES[name]:
+            raise ValueError(f"opensfm_amd.compat: {name!r} is registered as {target!r}: ask for one of them, not both")
+        wanted[target] = EXTRA_MODULES[name]
     for name, gpu in wanted.items():
         full = f"{package}.{name}"
         compiled = None
@@ -66,3 +72,8 @@ def install(package: str = "opensfm", force: bool = False, extra: Sequence[str] 
 def install_dense(package: str = "opensfm", force: bool = False) -> Dict[str, types.ModuleType]:
     """``install(package, force, extra=("pydense",))``: the default modules and ``<package>.pydense``"""
     return install(package, force, extra=("pydense",))
+
+
+def install_dense_full(package: str = "opensfm", force: bool = False) -> Dict[str, types.ModuleType]:
+    """``install(package, force, extra=("pydense_full",))``: the default modules and ``<package>.pydense`` with ``DepthmapPruner``"""
+    return install(package, force, extra=("pydense_full",))

@@ -1,6 +1,7 @@
 """``pydense`` (``opensfm/src/dense/python/pybind.cc``): ``DepthmapEstimator`` and ``DepthmapCleaner`` with the wrapper's method names and
-argument order (``depthmap_bind.h``), served by ``osfm_depthmap_estimate`` / ``osfm_depthmap_clean``.  ``DepthmapPruner`` and
-``OpenMVSExporter`` are not provided (an ordered host-side compaction and file writing): the overlay's ``AttributeError`` names them.
+argument order (``depthmap_bind.h``), served by ``osfm_depthmap_estimate`` / ``osfm_depthmap_clean``.  ``DepthmapPruner`` is not part of
+this module's surface (``compat.pydense_full`` adds it) and ``OpenMVSExporter`` (file writing) is not provided: the overlay's
+``AttributeError`` names them.
 
 One addition: a ``seed`` property.  The reference seeds itself from ``random_device``; here a run is reproducible, and the default seed
 is fixed."""

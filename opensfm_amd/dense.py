@@ -1,9 +1,11 @@
-"""Raw depthmaps and their cleaning on the GPU (``opensfm/dense.py`` compute_depthmap / clean_depthmap, ``dense::DepthmapEstimator`` and
-``dense::DepthmapCleaner``) for a batch of shots in one call of ``osfm_depthmap_estimate`` / ``osfm_depthmap_clean``.
+"""Raw depthmaps, their cleaning, pruning and merging on the GPU (``opensfm/dense.py`` compute_depthmap / clean_depthmap / prune_depthmap /
+merge_depthmaps, ``dense::DepthmapEstimator``, ``dense::DepthmapCleaner`` and ``dense::DepthmapPruner``) for a batch of shots in one call
+of ``osfm_depthmap_estimate`` / ``osfm_depthmap_clean`` / ``osfm_depthmap_prune``.
 
 A problem of the estimator is ``{"views": [(K, R, t, image, mask), ...], "min_depth": float, "max_depth": float}`` with the shot itself
-first, as ``add_views_to_depth_estimator`` adds them; of the cleaner ``{"views": [(K, R, t, depth), ...]}``.  K, R are 3 x 3, t has 3
-entries; images and masks are uint8 (height, width), depths float32.  There is no CPU fallback."""
+first, as ``add_views_to_depth_estimator`` adds them; of the cleaner ``{"views": [(K, R, t, depth), ...]}``; of the pruner
+``{"views": [(K, R, t, depth, plane, color, label), ...]}``.  K, R are 3 x 3, t has 3 entries; images, masks and labels are uint8
+(height, width), depths float32, planes float32 (height, width, 3), colors uint8 (height, width, 3).  There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -139,3 +141,70 @@ def compute_depthmaps_arrays(problems: Sequence[dict], config: Optional[dict] = 
 def clean_depthmaps_arrays(problems: Sequence[dict], config: Optional[dict] = None, device: Optional[int] = None) -> List[np.ndarray]:
     """``dense.clean_depthmap`` for every problem"""
     return clean_raw(problems, params_from_config(config), device)[0]
+
+
+def _pack_prune_views(problems):
+    """``_pack_views`` for the pruner's four arrays per view (two dtypes, two of them with three channels); the messages are the
+    wrapper's (depthmap_bind.h:113-124)"""
+    offsets = np.zeros(len(problems) + 1, np.int32)
+    K, R, t, data, widths, heights = [], [], [], [[], [], [], []], [], []
+    for b, problem in enumerate(problems):
+        views = problem["views"]
+        offsets[b + 1] = offsets[b] + len(views)
+        for view in views:
+            K.append(np.asarray(view[0], np.float64).reshape(9))
+            R.append(np.asarray(view[1], np.float64).reshape(9))
+            t.append(np.asarray(view[2], np.float64).reshape(3))
+            depth, plane = np.ascontiguousarray(view[3], np.float32), np.ascontiguousarray(view[4], np.float32)
+            color, label = np.ascontiguousarray(view[5], np.uint8), np.ascontiguousarray(view[6], np.uint8)
+            if depth.ndim != 2:
+                raise ValueError("a view's depth must be a (height, width) array")
+            for name, a, channels in (("plane", plane, 3), ("color", color, 3), ("label", label, 0)):
+                if a.shape[:2] != depth.shape:
+                    raise ValueError(f"depth and {name} must have matching shapes.")
+                if a.shape[2:] != ((channels,) if channels else ()):
+                    raise ValueError(f"a view's {name} must be a (height, width" + (f", {channels})" if channels else ")") + " array")
+            for k, a in enumerate((depth, plane, color, label)):
+                data[k].append(a)
+            heights.append(depth.shape[0])
+            widths.append(depth.shape[1])
+    flat = [np.ascontiguousarray(np.concatenate(x) if x else np.zeros(0), np.float64) for x in (K, R, t)]
+    return offsets, flat, data, np.asarray(widths, np.int32), np.asarray(heights, np.int32)
+
+
+Cloud = Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]
+
+
+def prune_raw(problems: Sequence[dict], params: _lib.DepthmapParams, device: Optional[int] = None) -> Tuple[Cloud, np.ndarray, float]:
+    """``osfm_depthmap_prune``: the merged cloud of the batch -- points (n, 3) float32, normals (n, 3) float32, colors (n, 3) uint8,
+    labels (n,) uint8, the rows of problem 0 first --, the rows of every problem and the kernel ms"""
+    offsets, (K, R, t), (depths, planes, colors, labels), widths, heights = _pack_prune_views(problems)
+    first = [depths[offsets[b]] for b, problem in enumerate(problems) if len(problem["views"])]
+    capacity = int(sum(np.count_nonzero(~(d <= 0)) for d in first))  # depth > 0 or NaN: the pixels Prune does not skip
+    points, normals = np.empty((capacity, 3), np.float32), np.empty((capacity, 3), np.float32)
+    out_colors, out_labels = np.empty((capacity, 3), np.uint8), np.empty(capacity, np.uint8)
+    counts = np.zeros(len(problems), np.int64)
+    ms = C.c_double(0.0)
+    ctx = _lib.default_context(device)
+    _lib.check(_lib.load().osfm_depthmap_prune(
+        ctx.handle, len(problems), _dptr(offsets, C.c_int32), _dptr(K, C.c_double), _dptr(R, C.c_double), _dptr(t, C.c_double), _pointers(depths),
+        _pointers(planes), _pointers(colors), _pointers(labels), _dptr(widths, C.c_int32), _dptr(heights, C.c_int32), C.byref(params),
+        C.c_int64(capacity), _dptr(points, C.c_float), _dptr(normals, C.c_float), _dptr(out_colors, C.c_uint8), _dptr(out_labels, C.c_uint8),
+        _dptr(counts, C.c_int64), C.byref(ms)), "osfm_depthmap_prune")
+    n = int(counts.sum())
+    return (points[:n], normals[:n], out_colors[:n], out_labels[:n]), counts, ms.value
+
+
+def prune_depthmaps_arrays(problems: Sequence[dict], config: Optional[dict] = None, device: Optional[int] = None) -> List[Cloud]:
+    """``dense.prune_depthmap`` for every problem: per problem (points, normals, colors, labels), views into the merged buffers"""
+    merged, counts, _ = prune_raw(problems, params_from_config(config), device)
+    ends = np.cumsum(counts)
+    return [tuple(a[e - c:e] for a in merged) for c, e in zip(counts, ends)]
+
+
+def merge_depthmaps_arrays(problems: Sequence[dict], config: Optional[dict] = None, device: Optional[int] = None) -> Cloud:
+    """``dense.prune_depthmap`` for every problem and ``dense.merge_depthmaps`` of the results: the four concatenated arrays (no
+    problems: four empty arrays, as ``merge_depthmaps_from_provider`` returns)"""
+    if not len(problems):
+        return np.array([]), np.array([]), np.array([]), np.array([])
+    return prune_raw(problems, params_from_config(config), device)[0]
