@@ -480,6 +480,64 @@ int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, 
                              osfm_relrot_result *results, uint8_t *mask_or_null, double *kernel_ms /* may be NULL */);
 
 /* =====================================================================================
+ * Two-view 5-point reconstruction of candidate initial pairs (reconstruction.bootstrap_reconstruction ->
+ * two_view_reconstruction_general, opensfm/reconstruction.py:488-534, without its plane-based branch): a batch of ranked pairs in one
+ * call.  twoview.hip / twoview_core.h; no solver of its own -- the LO-RANSAC is osfm_relpose_pairs' (mode OSFM_RELPOSE_RANSAC, its
+ * results stay on the device), the inlier test, the rand() picks, the TinySolver refinement and the angle-axis are the leaves of
+ * relpose_core.h that the calibrated matcher is pinned on.  tv_config_kernel: one wavefront per (pair, configuration);
+ * tv_decide_kernel: one thread per pair.  A host build of twoview_core.h is held bit for bit to a restatement composed from the CPU
+ * oracle's leaves (tests/test_twoview_host.py); the GPU to that host build: statuses, choices, masks and the RANSAC bit for bit, the
+ * refined poses to 1e-6 (tests/test_gpu_twoview.py).
+ *
+ * osfm_two_view_pairs   pair p owns the correspondences offsets[p] .. offsets[p+1]-1 of the bearings b1 / b2 (total x 3).
+ *   poses == NULL: multiview.relative_pose_ransac(b1, b2, threshold, ransac_iterations, .) (multiview.py:494-516: R = R_lo^T,
+ *     t = -R_lo^T t_lo of the RANSAC's lo_model), then two_view_reconstruction_5pt on that pose.
+ *   poses given (n_pairs x 12: R row-major, then t): two_view_reconstruction_5pt(b1, b2, R, t, threshold, refine_iterations,
+ *     check_reversal, reversal_ratio) (reconstruction.py:415-485); no RANSAC runs.
+ *   Per configuration (0: the pose as given; 1, only with check_reversal: R^T, -R^T t) two_view_reconstruction_and_refinement
+ *   (reconstruction.py:336-374): compute_inliers_bearings, with more than 5 inliers relative_pose_optimize_nonlinear on them
+ *   (srand(42) restarts per refinement, as in the reference) and the inliers again.  result.R[c] / t[c]: R_curr^T (what the
+ *   reference hands to cv2.Rodrigues) and -R_curr^T t_curr.  Then the choice (reconstruction.py:458-485): a configuration counts
+ *   with more than 5 inliers; of two, min / max > reversal_ratio is undecidable, else the one with more inliers, a tie picking
+ *   configuration 1.  rotation: ceres' RotationMatrixToAngleAxis of the chosen R (cv2.Rodrigues' bit patterns are not pinned).
+ *   mask (total bytes): bit 0 / 1 = inlier of configuration 0 / 1, bit 2 = inlier of the chosen configuration.
+ *   A pair of 5 or fewer correspondences can never count: OSFM_TWO_VIEW_NO_CONFIGURATION, n_inliers -1, no work (it reaches
+ *   neither the RANSAC nor the device).  n_pairs == 0 returns OSFM_OK and touches nothing.  Arguments are checked as by
+ *   osfm_relpose_pairs (OSFM_E_INVALID: n_pairs < 0, offsets that do not start at 0 or descend, null bearings).
+ * osfm_two_view_pairs_pixels   the same from normalised image coordinates p1 / p2 (total x 2) and the camera table of
+ *   osfm_relrot_pairs_pixels (pair_cams[2p], pair_cams[2p+1]; cam_model[n_cams]; cam_params[n_cams x 16]); kernel_ms then includes
+ *   the bearings.
+ * ===================================================================================== */
+enum { OSFM_TWO_VIEW_OK = 0, OSFM_TWO_VIEW_NO_CONFIGURATION = 1, OSFM_TWO_VIEW_UNDECIDABLE = 2 };
+typedef struct osfm_two_view_params {
+  double threshold;          /* radians: config five_point_algo_threshold (0.004) */
+  double probability;        /* RobustEstimatorParams::probability (0.99: relative_pose_ransac never passes its 0.999 on) */
+  double reversal_ratio;     /* config five_point_reversal_ratio (0.95) */
+  int32_t ransac_iterations; /* 1000 (reconstruction.py:522) */
+  int32_t use_lo;            /* RobustEstimatorParams::use_local_optimization (1) */
+  int32_t lo_iterations;     /* ::local_optimization_iterations (10) */
+  int32_t refine_iterations; /* config five_point_refine_rec_iterations (1000) */
+  int32_t check_reversal;    /* config five_point_reversal_check */
+  int32_t skip_inlier_tests; /* 0.  1: every correspondence counts as an inlier before and after the refinement -- configuration 0
+                                on a given pose is then pygeometry.relative_pose_refinement on its own */
+} osfm_two_view_params;
+typedef struct osfm_two_view_result {
+  double R[2][9], t[2][3];            /* per configuration (zeros for one that was not run) */
+  double rotation[3], translation[3]; /* the chosen configuration: angle-axis of its R, its t; zeros unless status is OK */
+  double lo_model[12];                /* the RANSAC's ScoreInfo::lo_model (zeros on given poses) */
+  int32_t status, chosen;             /* OSFM_TWO_VIEW_*; -1, 0 or 1 */
+  int32_t n_inliers[2];               /* per configuration; -1 when not run */
+  int32_t refine_iterations[2];       /* TinySolver iterations per configuration (0: not refined) */
+  int32_t score, iterations;          /* best inlier count of the RANSAC, iterations it ran (zeros on given poses) */
+} osfm_two_view_result;
+int osfm_two_view_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const int64_t *offsets, int n_pairs, const double *poses_or_null,
+                        const osfm_two_view_params *params, osfm_two_view_result *results, uint8_t *mask,
+                        double *kernel_ms /* may be NULL: HIP-event time of the kernels */);
+int osfm_two_view_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, const int64_t *offsets, int n_pairs, const int32_t *pair_cams,
+                               const int32_t *cam_model, const double *cam_params, int n_cams, const double *poses_or_null,
+                               const osfm_two_view_params *params, osfm_two_view_result *results, uint8_t *mask, double *kernel_ms /* may be NULL */);
+
+/* =====================================================================================
  * Absolute-pose (P3P) LO-RANSAC of candidate images (reconstruction.resect, opensfm/reconstruction.py:695-762): the step of
  * grow_reconstruction that adds an image to the map.  abspose.hip / abspose_core.h, the same walk (loransac_walk.h): one wavefront per image (lane 0 draws the next
  * block of samples, four lanes per sample solve one root of the three-point solver's quartic each, the wavefront scores every model

@@ -77,6 +77,36 @@ class RelrotResult(C.Structure):
     ]
 
 
+class TwoViewParams(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("probability", C.c_double),
+        ("reversal_ratio", C.c_double),
+        ("ransac_iterations", C.c_int32),
+        ("use_lo", C.c_int32),
+        ("lo_iterations", C.c_int32),
+        ("refine_iterations", C.c_int32),
+        ("check_reversal", C.c_int32),
+        ("skip_inlier_tests", C.c_int32),
+    ]
+
+
+class TwoViewResult(C.Structure):
+    _fields_ = [
+        ("R", C.c_double * 18),
+        ("t", C.c_double * 6),
+        ("rotation", C.c_double * 3),
+        ("translation", C.c_double * 3),
+        ("lo_model", C.c_double * 12),
+        ("status", C.c_int32),
+        ("chosen", C.c_int32),
+        ("n_inliers", C.c_int32 * 2),
+        ("refine_iterations", C.c_int32 * 2),
+        ("score", C.c_int32),
+        ("iterations", C.c_int32),
+    ]
+
+
 AbsposeParams = RelrotParams  # osfm_abspose_params has the fields of osfm_relrot_params
 
 
@@ -207,6 +237,17 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
          C.POINTER(C.c_double), C.c_int, C.POINTER(RelrotParams), C.POINTER(RelrotResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_two_view_pairs": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_double), C.POINTER(TwoViewParams),
+         C.POINTER(TwoViewResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_two_view_pairs_pixels": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(TwoViewParams), C.POINTER(TwoViewResult), C.POINTER(C.c_uint8),
+         C.POINTER(C.c_double)],
     ),
     "osfm_abspose_images": (
         C.c_int,

@@ -1,6 +1,7 @@
 """Leaves of the reference's ``pygeometry`` (``opensfm/src/geometry/python/pybind.cc``) under its argument names:
 ``triangulate_bearings_midpoint`` and ``point_refinement``, served by ``triangulate.hip``, and ``absolute_pose_three_points`` and
-``absolute_pose_n_points``, served by ``abspose.hip``.  One call is one track on the GPU -- these exist so that
+``absolute_pose_n_points``, served by ``abspose.hip``, and ``relative_pose_refinement``, served by ``twoview.hip``.  One call is one
+track (or pair) on the GPU -- these exist so that
 code written against the leaves (``TrackTriangulator``) runs unchanged; the batched path is
 ``opensfm_amd.reconstruction.triangulate_shot_features`` / ``retriangulate``.
 
@@ -54,6 +55,21 @@ def point_refinement(centers, bearings, point, iterations: int) -> np.ndarray:
                                            ptr(initial, C.c_double), int(iterations), ptr(out, C.c_double), ptr(used, C.c_int32), C.byref(ms)),
            "osfm_triangulate_refine")
     return out
+
+
+def relative_pose_refinement(Rt, b1, b2, iterations: int) -> np.ndarray:
+    """``geometry::RelativePoseRefinement`` (relative_pose.h:149-183): the 3 x 4 pose [R | t] refined by TinySolver over 100 rand()-picked
+    correspondences, ``multiview.relative_pose_optimize_nonlinear`` runs unchanged on it.  Served by ``twoview.hip``: one pair, the
+    given pose, every correspondence counted as an inlier.  The device call takes and returns the inverse pose, so Rt is inverted going
+    in and coming out (two roundings of the translation, ~1e-16).  Needs at least 6 correspondences (a smaller pair never reaches the
+    device)."""
+    Rt = np.asarray(Rt, np.float64).reshape(3, 4)
+    b1 = np.ascontiguousarray(b1, np.float64).reshape(-1, 3)
+    if len(b1) < 6:
+        raise NotImplementedError("relative_pose_refinement: fewer than 6 correspondences are not refined on the GPU path")
+    pose = np.r_[Rt[:, :3].T.reshape(9), -Rt[:, :3].T.dot(Rt[:, 3])]
+    res, _, _ = _reconstruction.two_view_pairs(b1, b2, [0, len(b1)], 1.0, poses=pose, refine_iterations=iterations, skip_inlier_tests=True)
+    return np.c_[res[0]["R"][0], res[0]["t"][0]]
 
 
 def _abspose_solve(bearings, points, kind: int, who: str):

@@ -357,6 +357,10 @@ int osfm_launch_match(osfm_ctx *ctx, const osfm_store *store, const int32_t *d_p
 // relpose.hip: the LO-RANSAC rounds (+ refinement in MATCH mode) over device-resident bearings; fills d_mask and d_out
 int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *d_b2, const int64_t *d_off, const int64_t *offsets,
                             int n_pairs, const osfm_relpose_params *prm, int mode, uint8_t *d_mask, void *d_out, int *rounds_out);
+// relrot.hip: the bearings of both sides of every pair from normalised image coordinates (d_p1 / d_p2: total x 2) and a camera table,
+// pair p's cameras d_pair_cams[2p], [2p+1]; everything device-resident, enqueued on st
+void osfm_launch_pair_bearings(hipStream_t st, int n_pairs, const double *d_p1, const double *d_p2, const int64_t *d_off, const int32_t *d_pair_cams,
+                               const int32_t *d_cam_model, const double *d_cam_params, double *d_b1, double *d_b2);
 // calib.hip: the geometric stage of the calibrated branch on a chunk's device buffers (in place, like osfm_launch_ransac_pairs)
 struct OsfmCalibStage {
   const double *d_bearings;  // unit bearings of every feature of the store, padded tile layout (tile * 32 + row) x 3

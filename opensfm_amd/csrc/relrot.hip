@@ -59,6 +59,13 @@ int run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *
 
 }  // namespace
 
+// rr_bearings_kernel for the pair drivers (this file's, twoview.hip's): everything device-resident, enqueued on st
+void osfm_launch_pair_bearings(hipStream_t st, int n_pairs, const double *d_p1, const double *d_p2, const int64_t *d_off, const int32_t *d_pair_cams,
+                               const int32_t *d_cam_model, const double *d_cam_params, double *d_b1, double *d_b2) {
+  hipLaunchKernelGGL(rr_bearings_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, d_p1, d_p2, d_off, d_pair_cams, d_cam_model, d_cam_params, d_b1,
+                     d_b2);
+}
+
 extern "C" int osfm_relrot_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const int64_t *offsets, int n_pairs,
                                  const osfm_relrot_params *prm, osfm_relrot_result *results, uint8_t *mask, double *kernel_ms) {
   if (kernel_ms) *kernel_ms = 0.0;
@@ -110,8 +117,8 @@ extern "C" int osfm_relrot_pairs_pixels(osfm_ctx *ctx, const double *p1, const d
   OSFM_HIP(hipMemcpyAsync(d_cm.p, cam_model, (size_t)n_cams * 4, hipMemcpyHostToDevice, st));
   OSFM_HIP(hipMemcpyAsync(d_cp.p, cam_params, (size_t)n_cams * 16 * 8, hipMemcpyHostToDevice, st));
   OSFM_HIP(hipEventRecord(ctx->ev[0], st));  // the kernel time includes the bearings
-  hipLaunchKernelGGL(rr_bearings_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, d_p1.as<double>(), d_p2.as<double>(), d_off.as<int64_t>(),
-                     d_pc.as<int32_t>(), d_cm.as<int32_t>(), d_cp.as<double>(), d_b1.as<double>(), d_b2.as<double>());
+  osfm_launch_pair_bearings(st, n_pairs, d_p1.as<double>(), d_p2.as<double>(), d_off.as<int64_t>(), d_pc.as<int32_t>(), d_cm.as<int32_t>(),
+                            d_cp.as<double>(), d_b1.as<double>(), d_b2.as<double>());
   OSFM_HIP(hipGetLastError());
   return run_device(ctx, st, d_b1.as<double>(), d_b2.as<double>(), d_off.as<int64_t>(), offsets, n_pairs, prm, results, mask, true, kernel_ms);
 }

@@ -17,7 +17,14 @@ estimator on flat arrays and ``absolute_pose_ransac`` is ``multiview.absolute_po
 
 ``cull_final_point_cloud(reconstruction, config)`` is the tail of ``grow_reconstruction`` after its last bundle
 (``reconstruction.py:1586-1594``): the outlier step (``discard_gross_observations``) and, under ``filter_final_point_cloud``, the two point-cloud filters on the GPU
-(``cloud.hip``)."""
+(``cloud.hip``).
+
+``two_view_reconstruction_general(p1, p2, camera1, camera2, threshold, iterations, check_reversal, reversal_ratio)``
+(``reconstruction.py:488-560``) turns a ranked pair into the first two poses: bearings, 5-point LO-RANSAC, both configurations of
+``two_view_reconstruction_5pt`` and the choice between them in one GPU call (``twoview.hip``); ``two_view_reconstruction_general_pairs`` does
+that for the first K ranked pairs at once, ``two_view_pairs`` / ``two_view_pairs_pixels`` are the same calls on flat arrays, and
+``two_view_reconstruction_and_refinement`` / ``two_view_reconstruction_5pt`` are the reference's functions on given poses.  The
+plane-based branch stays on the host (an optional callable)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,7 +33,8 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Set,
 
 import numpy as np
 
-from ._lib import AbsposeParams, AbsposeResult, RelrotParams, RelrotResult, TriangulateParams, check, default_context, load
+from ._lib import (AbsposeParams, AbsposeResult, RelrotParams, RelrotResult, TriangulateParams, TwoViewParams, TwoViewResult, check,
+                   default_context, load)
 from .matching import camera_parameters
 
 
@@ -674,3 +682,228 @@ def resect_candidates(data, tracks_manager, reconstruction, candidates: Sequence
                 return {"image": image, "new_shots": new_shots, "report": report, "failed": failed}
             failed.append((image, report))
     return {"image": None, "new_shots": set(), "report": None, "failed": failed}
+
+
+# ------------------------------------------------------------------------------------------------
+# bootstrap: the two-view 5-point reconstruction of candidate initial pairs (reconstruction.py:336-560)
+# ------------------------------------------------------------------------------------------------
+TWO_VIEW_STATUS = ("ok", "no configuration", "undecidable")
+
+
+def _two_view_params(threshold: float, refine_iterations: int, check_reversal: bool, reversal_ratio: float, iterations: int, probability: float,
+                     skip_inlier_tests: bool = False) -> TwoViewParams:
+    return TwoViewParams(float(threshold), float(probability), float(reversal_ratio), int(iterations), 1, 10, int(refine_iterations),
+                         int(bool(check_reversal)), int(bool(skip_inlier_tests)))
+
+
+def _two_view_poses(poses, n_pairs: int, who: str):
+    if poses is None:
+        return None, C.POINTER(C.c_double)()
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+    if len(poses) != n_pairs:
+        raise ValueError(who + ": poses must be n_pairs x 12 (R row-major, then t)")
+    return poses, _fptr(poses, C.c_double)
+
+
+def _two_view_results(res, n_pairs: int) -> List[Dict[str, Any]]:
+    out = []
+    for p in range(n_pairs):
+        r = res[p]
+        out.append({"status": r.status, "chosen": r.chosen, "R": np.array(r.R).reshape(2, 3, 3), "t": np.array(r.t).reshape(2, 3),
+                    "n_inliers": list(r.n_inliers), "refine_iterations": list(r.refine_iterations), "rotation": np.array(r.rotation),
+                    "translation": np.array(r.translation), "lo_model": np.array(r.lo_model).reshape(3, 4), "score": r.score,
+                    "iterations": r.iterations})
+    return out
+
+
+def two_view_pairs(b1: np.ndarray, b2: np.ndarray, offsets: Sequence[int], threshold: float, *, poses=None, refine_iterations: int = 1000,
+                   check_reversal: bool = False, reversal_ratio: float = 1.0, iterations: int = 1000, probability: float = 0.99,
+                   skip_inlier_tests: bool = False, ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, float]:
+    """``osfm_two_view_pairs``: the 5-point half of ``two_view_reconstruction_general`` for a batch of pairs on bearings (pair p owns rows
+    offsets[p]:offsets[p+1] of b1 / b2), or, with `poses` (n_pairs x 12: R row-major, then t), ``two_view_reconstruction_5pt`` on given poses.
+    -> (per-pair dicts: status (index into TWO_VIEW_STATUS), chosen (-1, 0, 1), R / t / n_inliers / refine_iterations per configuration,
+    rotation / translation of the chosen one, the RANSAC's lo_model / score / iterations; mask (uint8 per row: bit 0 / 1 inlier of
+    configuration 0 / 1, bit 2 of the chosen one); kernel milliseconds)."""
+    ctx = ctx or default_context()
+    b1 = np.ascontiguousarray(b1, np.float64).reshape(-1, 3)
+    b2 = np.ascontiguousarray(b2, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(b1) != len(b2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(b1)):
+        raise ValueError("two_view_pairs: b1 / b2 / offsets do not agree")
+    poses, poses_ptr = _two_view_poses(poses, n_pairs, "two_view_pairs")
+    prm = _two_view_params(threshold, refine_iterations, check_reversal, reversal_ratio, iterations, probability, skip_inlier_tests)
+    res = (TwoViewResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(b1), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_two_view_pairs(ctx.handle, _fptr(b1, C.c_double), _fptr(b2, C.c_double), _fptr(off, C.c_int64), n_pairs, poses_ptr,
+                                     C.byref(prm), res, _fptr(mask, C.c_uint8), C.byref(ms)), "osfm_two_view_pairs")
+    return _two_view_results(res, n_pairs), mask[: len(b1)], ms.value
+
+
+def two_view_pairs_pixels(p1: np.ndarray, p2: np.ndarray, offsets: Sequence[int], pair_cams: np.ndarray, cam_model: np.ndarray,
+                          cam_params: np.ndarray, threshold: float, *, poses=None, refine_iterations: int = 1000, check_reversal: bool = False,
+                          reversal_ratio: float = 1.0, iterations: int = 1000, probability: float = 0.99,
+                          ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, float]:
+    """``osfm_two_view_pairs_pixels``: the same from normalised image coordinates, the bearings computed on the device with the cameras
+    pair_cams[p] = (camera of side 1, camera of side 2) of the table cam_model (n_cams) / cam_params (n_cams x 16)."""
+    ctx = ctx or default_context()
+    p1 = np.ascontiguousarray(np.asarray(p1, np.float64).reshape(len(p1), -1)[:, :2])
+    p2 = np.ascontiguousarray(np.asarray(p2, np.float64).reshape(len(p2), -1)[:, :2])
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(p1) != len(p2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(p1)):
+        raise ValueError("two_view_pairs_pixels: p1 / p2 / offsets do not agree")
+    pc = np.ascontiguousarray(pair_cams, np.int32)
+    cm = np.ascontiguousarray(cam_model, np.int32)
+    cp = np.ascontiguousarray(cam_params, np.float64)
+    if pc.shape != (n_pairs, 2) or cm.ndim != 1 or cp.shape != (len(cm), 16):
+        raise ValueError(f"two_view_pairs_pixels: pair_cams must be ({n_pairs}, 2) and cam_params ({len(cm)}, 16) for cam_model of length "
+                         f"{len(cm)}; got {pc.shape}, {cp.shape}")
+    poses, poses_ptr = _two_view_poses(poses, n_pairs, "two_view_pairs_pixels")
+    prm = _two_view_params(threshold, refine_iterations, check_reversal, reversal_ratio, iterations, probability)
+    res = (TwoViewResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(p1), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_two_view_pairs_pixels(ctx.handle, _fptr(p1, C.c_double), _fptr(p2, C.c_double), _fptr(off, C.c_int64), n_pairs,
+                                            _fptr(pc, C.c_int32), _fptr(cm, C.c_int32), _fptr(cp, C.c_double), len(cm), poses_ptr, C.byref(prm), res,
+                                            _fptr(mask, C.c_uint8), C.byref(ms)), "osfm_two_view_pairs_pixels")
+    return _two_view_results(res, n_pairs), mask[: len(p1)], ms.value
+
+
+def _rotation_vector(R: np.ndarray) -> np.ndarray:
+    """angle-axis of a rotation matrix through the quaternion, as the library's rotmat_to_aa (for a configuration that was not chosen)"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    q = np.zeros(4)
+    trace = R[0, 0] + R[1, 1] + R[2, 2]
+    if trace >= 0.0:
+        s = np.sqrt(trace + 1.0)
+        q[0] = 0.5 * s
+        s = 0.5 / s
+        q[1:] = [(R[2, 1] - R[1, 2]) * s, (R[0, 2] - R[2, 0]) * s, (R[1, 0] - R[0, 1]) * s]
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+        q[i + 1] = 0.5 * s
+        s = 0.5 / s
+        q[0] = (R[k, j] - R[j, k]) * s
+        q[j + 1] = (R[j, i] + R[i, j]) * s
+        q[k + 1] = (R[k, i] + R[i, k]) * s
+    norm = float(np.sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]))
+    if norm > 0.0:
+        two_theta = 2.0 * (np.arctan2(-norm, -q[0]) if q[0] < 0.0 else np.arctan2(norm, q[0]))
+        return q[1:] * (two_theta / norm)
+    return q[1:] * 2.0
+
+
+def _triangulating_rows(b1: np.ndarray, b2: np.ndarray, R: np.ndarray, t: np.ndarray, threshold: float) -> np.ndarray:
+    """the library's inlier test (inlier_bearing: the midpoint of the two rays, seen from both cameras within `threshold`) in numpy, for
+    the handful of rows of a pair that is too small to reach the device -> indices"""
+    b1 = np.asarray(b1, np.float64).reshape(-1, 3)
+    b2 = np.asarray(b2, np.float64).reshape(-1, 3)
+    keep = []
+    for i, (x, y) in enumerate(zip(b1, b2)):
+        ry = R.dot(y)
+        a00, a10, a11 = x.dot(x), x.dot(ry), -ry.dot(ry)
+        det = a00 * a11 + a10 * a10
+        if -1e-10 < det < 1e-10:
+            continue
+        rhs0, rhs1 = t.dot(x), t.dot(ry)
+        X = 0.5 * ((a11 * rhs0 + a10 * rhs1) / det * x + t + (-a10 * rhs0 + a00 * rhs1) / det * ry)
+        q = R.T.dot(X - t)
+        if np.linalg.norm(X / np.linalg.norm(X) - x) < threshold and np.linalg.norm(q / np.linalg.norm(q) - y) < threshold:
+            keep.append(i)
+    return np.array(keep, np.int64)
+
+
+def two_view_reconstruction_and_refinement(b1: np.ndarray, b2: np.ndarray, R: np.ndarray, t: np.ndarray, threshold: float, iterations: int,
+                                           transposed: bool, ctx=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Reconstruct two views using the provided rotation and translation (``reconstruction.py:336-374``): same arguments, same return
+    (rotation vector, translation, inlier indices).  The rotation vector is the library's angle-axis of the matrix the reference hands to
+    ``cv2.Rodrigues``."""
+    pose = np.r_[np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)]
+    res, mask, _ = two_view_pairs(b1, b2, [0, len(b1)], threshold, poses=pose, refine_iterations=iterations, check_reversal=bool(transposed), ctx=ctx)
+    c = 1 if transposed else 0
+    if res[0]["n_inliers"][c] < 0:  # five or fewer correspondences: nothing ran, and nothing is refined in the reference either
+        R0, t0 = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
+        Rc, tc = (R0.T, -R0.T.dot(t0)) if transposed else (R0, t0)
+        return _rotation_vector(Rc.T), -Rc.T.dot(tc), _triangulating_rows(b1, b2, Rc, tc, threshold)
+    return _rotation_vector(res[0]["R"][c]), res[0]["t"][c].copy(), np.flatnonzero(mask >> c & 1)
+
+
+def two_view_reconstruction_5pt(b1: np.ndarray, b2: np.ndarray, R: np.ndarray, t: np.ndarray, threshold: float, iterations: int,
+                                check_reversal: bool = False, reversal_ratio: float = 1.0,
+                                ctx=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Any]:
+    """5-point reconstruction and refinement given the relative rotation and translation (``reconstruction.py:415-485``): same
+    arguments, same return -- (rotation vector, translation, inlier indices), or (None, None, []) where no configuration has more than
+    5 inliers or the two cannot be told apart."""
+    pose = np.r_[np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64).reshape(3)]
+    res, mask, _ = two_view_pairs(b1, b2, [0, len(b1)], threshold, poses=pose, refine_iterations=iterations, check_reversal=check_reversal,
+                                  reversal_ratio=reversal_ratio, ctx=ctx)
+    if res[0]["status"] != 0:
+        return None, None, []
+    return res[0]["rotation"], res[0]["translation"], np.flatnonzero(mask >> 2 & 1)
+
+
+def two_view_reconstruction_general_pairs(pairs: Sequence[Tuple[Any, Any, Any, Any]], threshold: float, iterations: int,
+                                          check_reversal: bool = False, reversal_ratio: float = 1.0, *,
+                                          plane_based: Optional[Callable] = None, ctx=None) -> List[Tuple[Any, Any, Any, Dict[str, Any]]]:
+    """``two_view_reconstruction_general`` (``reconstruction.py:488-560``) for a list of (p1, p2, camera1, camera2) in ONE GPU call: the
+    bearings, the 5-point LO-RANSAC, both configurations and the choice.  -> [(R, t, inliers, report)] as the reference returns them.
+    The plane-based branch (``cv2.findHomography``) is not on the GPU: ``plane_based(b1, b2, threshold) -> (R, t, inliers)`` may supply it
+    (the reference's own ``two_view_reconstruction_plane_based`` fits) and is then compared as the reference compares; without it that
+    branch counts as not valid with 0 inliers."""
+    from . import matching
+
+    if not pairs:
+        return []
+    cam_index: Dict[int, int] = {}
+    models: List[int] = []
+    params: List[np.ndarray] = []
+    pair_cams = np.zeros((len(pairs), 2), np.int32)
+    for k, (_, _, camera1, camera2) in enumerate(pairs):
+        for side, cam in enumerate((camera1, camera2)):
+            if id(cam) not in cam_index:
+                model, par = camera_parameters(cam)
+                cam_index[id(cam)] = len(models)
+                models.append(model)
+                params.append(par)
+            pair_cams[k, side] = cam_index[id(cam)]
+    p1 = np.concatenate([np.asarray(p[0], np.float64).reshape(len(p[0]), -1)[:, :2] for p in pairs])
+    p2 = np.concatenate([np.asarray(p[1], np.float64).reshape(len(p[1]), -1)[:, :2] for p in pairs])
+    off = np.r_[0, np.cumsum([len(p[0]) for p in pairs])].astype(np.int64)
+    # relative_pose_ransac(b1, b2, threshold, 1000, 0.999): the 0.999 is not passed on (multiview.py:494-516 sets only the iterations),
+    # so the probability is the default 0.99
+    res, mask, _ = two_view_pairs_pixels(p1, p2, off, pair_cams, np.array(models, np.int32), np.array(params, np.float64).reshape(-1, 16), threshold,
+                                         refine_iterations=iterations, check_reversal=check_reversal, reversal_ratio=reversal_ratio, iterations=1000,
+                                         probability=0.99, ctx=ctx)
+    out = []
+    for k, (q1, q2, camera1, camera2) in enumerate(pairs):
+        valid_5pt = res[k]["status"] == 0
+        inliers_5p = np.flatnonzero(mask[off[k]: off[k + 1]] >> 2 & 1) if valid_5pt else []
+        R_plane, t_plane, inliers_plane = None, None, []
+        if plane_based is not None:
+            R_plane, t_plane, inliers_plane = plane_based(matching.pixel_bearing_many(camera1, q1, ctx), matching.pixel_bearing_many(camera2, q2, ctx),
+                                                          threshold)
+        valid_plane = R_plane is not None and t_plane is not None
+        report: Dict[str, Any] = {"5_point_inliers": len(inliers_5p), "plane_based_inliers": len(inliers_plane)}
+        if valid_5pt and len(inliers_5p) > len(inliers_plane):
+            report["method"] = "5_point"
+            out.append((res[k]["rotation"], res[k]["translation"], inliers_5p, report))
+        elif valid_plane:
+            report["method"] = "plane_based"
+            out.append((R_plane, t_plane, inliers_plane, report))
+        else:
+            report["decision"] = "Could not find initial motion"
+            out.append((None, None, [], report))
+    return out
+
+
+def two_view_reconstruction_general(p1: np.ndarray, p2: np.ndarray, camera1, camera2, threshold: float, iterations: int,
+                                    check_reversal: bool = False, reversal_ratio: float = 1.0, *, plane_based: Optional[Callable] = None,
+                                    ctx=None) -> Tuple[Any, Any, Any, Dict[str, Any]]:
+    """Reconstruct two views from point correspondences (``reconstruction.py:488-560``): same arguments, same return
+    (rotation vector, translation, inliers, report).  See two_view_reconstruction_general_pairs for `plane_based`."""
+    return two_view_reconstruction_general_pairs([(p1, p2, camera1, camera2)], threshold, iterations, check_reversal, reversal_ratio,
+                                                 plane_based=plane_based, ctx=ctx)[0]
