@@ -538,6 +538,61 @@ int osfm_two_view_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2
                                const osfm_two_view_params *params, osfm_two_view_result *results, uint8_t *mask, double *kernel_ms /* may be NULL */);
 
 /* =====================================================================================
+ * Plane-based two-view reconstruction of candidate initial pairs: the other half of two_view_reconstruction_general
+ * (reconstruction.two_view_reconstruction_plane_based, opensfm/reconstruction.py:298-333), a batch of ranked pairs in one call.
+ * plane.hip / plane_core.h.  pl_ransac_kernel: one wavefront per pair -- x = (b0 / b2, b1 / b2) per side (multiview.euclidean), a
+ * homography by this project's LO-RANSAC walk (loransac_walk.h; std::mt19937(42), 4-point samples, one model per sample, LO on every
+ * new or tied best with >= 4 inliers, ShouldStop with exponent 4) over a normalised DLT with cv2.findHomography's inlier test (one-way
+ * transfer error in the second image below the threshold), a final fit over all inliers kept when it has at least as many, H scaled
+ * to middle singular value 1 and positive determinant, multiview.motion_from_plane_homography restated (multiview.py:366-441) with the
+ * signs of the singular vectors fixed.  pl_motion_kernel: one wavefront per (pair, motion), compute_inliers_bearings with R^T, -R^T t.
+ * pl_decide_kernel: one thread per pair.  NOT cv2's RANSAC, refit with LM or float32 points (plane_core.h says what is and is not
+ * restated), and the motion returned is the one with the most inliers, the lowest index on ties -- the reference's np.argmax over a
+ * map object always returns motion 0.  A host build of plane_core.h is held to a numpy restatement (tests/test_plane_host.py), the
+ * GPU to that host build bit for bit (tests/test_gpu_plane.py).
+ *
+ * osfm_two_view_plane_pairs   pair p owns the correspondences offsets[p] .. offsets[p+1]-1 of the bearings b1 / b2 (total x 3).  A row
+ *   with b2 <= 0 on either side keeps its place and is an inlier of no homography.  status: OSFM_PLANE_OK; NO_HOMOGRAPHY: no model
+ *   with at least 4 inliers (H, singular zero, h_inliers 0); DEGENERATE: the reference's "two singular values within 1.0001" (pure
+ *   rotation, a plane through a camera centre) or H of rank below 2 (H, singular and h_inliers are reported).  Unless OK: chosen -1,
+ *   motion_inliers, R, t, rotation, translation zero.  R, t: the picked motion (x2 ~ R x1 + t, t in units of the plane's distance);
+ *   rotation: ceres' RotationMatrixToAngleAxis of R (the reference applies cv2.Rodrigues to R, not to R^T).
+ *   mask (total bytes): bit 0 = inlier of H, bit 1 = inlier of the picked motion.
+ *   A pair of fewer than 4 correspondences never reaches the device: NO_HOMOGRAPHY, chosen -1, mask 0.  n_pairs == 0 returns OSFM_OK
+ *   and touches nothing.  OSFM_E_INVALID (null arguments, offsets that do not start at 0 or descend, threshold <= 0, a camera outside
+ *   the table): no output is touched, kernel_ms included.
+ * osfm_two_view_plane_pairs_pixels   the same from normalised image coordinates p1 / p2 (total x 2) and the camera table of
+ *   osfm_two_view_pairs_pixels; kernel_ms then includes the bearings.
+ * osfm_homography_solve   the leaf: the normalised DLT over all n >= 4 rows of x1 / x2 (n x 2), *ok_out 0 (H_out zero) or 1.
+ * osfm_plane_motions   the leaf: the decomposition of H (row-major); motions_out: 8 x (R (9), t (3), n (3), d), *count_out 0 or 8.
+ * ===================================================================================== */
+enum { OSFM_PLANE_OK = 0, OSFM_PLANE_NO_HOMOGRAPHY = 1, OSFM_PLANE_DEGENERATE = 2 };
+typedef struct osfm_plane_params {
+  double threshold;                /* of the transfer error (normalised coordinates) and of the bearings' test (radians): 0.004 */
+  double probability;              /* RobustEstimatorParams::probability (0.99) */
+  int32_t iterations;              /* ::iterations (1000) */
+  int32_t use_lo;                  /* ::use_local_optimization (1) */
+  int32_t lo_iterations;           /* ::local_optimization_iterations (10) */
+  int32_t use_iteration_reduction; /* ::use_iteration_reduction (1) */
+} osfm_plane_params;
+typedef struct osfm_plane_result {
+  double H[9], singular[3];                        /* the homography (row-major) and its singular values (middle one 1) */
+  double R[9], t[3], rotation[3], translation[3];  /* the picked motion; rotation: angle-axis of R, translation: t */
+  int32_t status, chosen;                          /* OSFM_PLANE_*; -1 or 0 .. 7 */
+  int32_t h_inliers, iterations, n_inliers;        /* inliers of H, iterations of the walk, inliers of the picked motion */
+  int32_t motion_inliers[8];                       /* per motion, in the reference's loop order */
+  int32_t pad;
+} osfm_plane_result;
+int osfm_two_view_plane_pairs(osfm_ctx *ctx, const double *b1, const double *b2, const int64_t *offsets, int n_pairs,
+                              const osfm_plane_params *params, osfm_plane_result *results, uint8_t *mask,
+                              double *kernel_ms /* may be NULL: HIP-event time of the kernels */);
+int osfm_two_view_plane_pairs_pixels(osfm_ctx *ctx, const double *p1, const double *p2, const int64_t *offsets, int n_pairs,
+                                     const int32_t *pair_cams, const int32_t *cam_model, const double *cam_params, int n_cams,
+                                     const osfm_plane_params *params, osfm_plane_result *results, uint8_t *mask, double *kernel_ms /* may be NULL */);
+int osfm_homography_solve(osfm_ctx *ctx, const double *x1, const double *x2, int n, double *H_out, int *ok_out);
+int osfm_plane_motions(osfm_ctx *ctx, const double *H, double *motions_out /* 8 x 16 doubles */, int *count_out);
+
+/* =====================================================================================
  * Absolute-pose (P3P) LO-RANSAC of candidate images (reconstruction.resect, opensfm/reconstruction.py:695-762): the step of
  * grow_reconstruction that adds an image to the map.  abspose.hip / abspose_core.h, the same walk (loransac_walk.h): one wavefront per image (lane 0 draws the next
  * block of samples, four lanes per sample solve one root of the three-point solver's quartic each, the wavefront scores every model

@@ -107,6 +107,35 @@ class TwoViewResult(C.Structure):
     ]
 
 
+class PlaneParams(C.Structure):
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("probability", C.c_double),
+        ("iterations", C.c_int32),
+        ("use_lo", C.c_int32),
+        ("lo_iterations", C.c_int32),
+        ("use_iteration_reduction", C.c_int32),
+    ]
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [
+        ("H", C.c_double * 9),
+        ("singular", C.c_double * 3),
+        ("R", C.c_double * 9),
+        ("t", C.c_double * 3),
+        ("rotation", C.c_double * 3),
+        ("translation", C.c_double * 3),
+        ("status", C.c_int32),
+        ("chosen", C.c_int32),
+        ("h_inliers", C.c_int32),
+        ("iterations", C.c_int32),
+        ("n_inliers", C.c_int32),
+        ("motion_inliers", C.c_int32 * 8),
+        ("pad", C.c_int32),
+    ]
+
+
 AbsposeParams = RelrotParams  # osfm_abspose_params has the fields of osfm_relrot_params
 
 
@@ -249,6 +278,19 @@ SIGNATURES = {
          C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(TwoViewParams), C.POINTER(TwoViewResult), C.POINTER(C.c_uint8),
          C.POINTER(C.c_double)],
     ),
+    "osfm_two_view_plane_pairs": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(PlaneParams), C.POINTER(PlaneResult),
+         C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_two_view_plane_pairs_pixels": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+         C.POINTER(C.c_double), C.c_int, C.POINTER(PlaneParams), C.POINTER(PlaneResult), C.POINTER(C.c_uint8), C.POINTER(C.c_double)],
+    ),
+    "osfm_homography_solve": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_int)]),
+    "osfm_plane_motions": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "osfm_abspose_images": (
         C.c_int,
         [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int, C.POINTER(AbsposeParams),

@@ -24,7 +24,9 @@ estimator on flat arrays and ``absolute_pose_ransac`` is ``multiview.absolute_po
 ``two_view_reconstruction_5pt`` and the choice between them in one GPU call (``twoview.hip``); ``two_view_reconstruction_general_pairs`` does
 that for the first K ranked pairs at once, ``two_view_pairs`` / ``two_view_pairs_pixels`` are the same calls on flat arrays, and
 ``two_view_reconstruction_and_refinement`` / ``two_view_reconstruction_5pt`` are the reference's functions on given poses.  The
-plane-based branch stays on the host (an optional callable)."""
+plane-based branch (``two_view_reconstruction_plane_based``, ``reconstruction.py:298-333``) runs on the GPU too (``plane.hip``) when
+``plane_based="device"`` is passed: one more call for the whole list; ``two_view_plane_pairs`` / ``two_view_plane_pairs_pixels`` are that
+call on flat arrays and ``motion_from_plane_homography`` is ``multiview.motion_from_plane_homography``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,8 +35,8 @@ from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Set,
 
 import numpy as np
 
-from ._lib import (AbsposeParams, AbsposeResult, RelrotParams, RelrotResult, TriangulateParams, TwoViewParams, TwoViewResult, check,
-                   default_context, load)
+from ._lib import (AbsposeParams, AbsposeResult, PlaneParams, PlaneResult, RelrotParams, RelrotResult, TriangulateParams, TwoViewParams,
+                   TwoViewResult, check, default_context, load)
 from .matching import camera_parameters
 
 
@@ -846,14 +848,114 @@ def two_view_reconstruction_5pt(b1: np.ndarray, b2: np.ndarray, R: np.ndarray, t
     return res[0]["rotation"], res[0]["translation"], np.flatnonzero(mask >> 2 & 1)
 
 
+# ------------------------------------------------------------------------------------------------
+# bootstrap: the plane-based two-view reconstruction (reconstruction.py:298-333, multiview.py:366-441)
+# ------------------------------------------------------------------------------------------------
+PLANE_STATUS = ("ok", "no homography", "degenerate homography")
+
+
+def _plane_params(threshold: float, iterations: int, probability: float, use_lo: bool, lo_iterations: int,
+                  use_iteration_reduction: bool) -> PlaneParams:
+    return PlaneParams(float(threshold), float(probability), int(iterations), int(bool(use_lo)), int(lo_iterations),
+                       int(bool(use_iteration_reduction)))
+
+
+def _plane_results(res, n_pairs: int) -> List[Dict[str, Any]]:
+    out = []
+    for p in range(n_pairs):
+        r = res[p]
+        out.append({"status": r.status, "H": np.array(r.H).reshape(3, 3), "singular": np.array(r.singular), "h_inliers": r.h_inliers,
+                    "iterations": r.iterations, "motion_inliers": list(r.motion_inliers), "chosen": r.chosen, "R": np.array(r.R).reshape(3, 3),
+                    "t": np.array(r.t), "rotation": np.array(r.rotation), "translation": np.array(r.translation), "n_inliers": r.n_inliers})
+    return out
+
+
+def two_view_plane_pairs(b1: np.ndarray, b2: np.ndarray, offsets: Sequence[int], threshold: float, *, iterations: int = 1000,
+                         probability: float = 0.99, use_lo: bool = True, lo_iterations: int = 10, use_iteration_reduction: bool = True,
+                         ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, float]:
+    """``osfm_two_view_plane_pairs``: ``two_view_reconstruction_plane_based`` for a batch of pairs on bearings (pair p owns rows
+    offsets[p]:offsets[p+1] of b1 / b2) -- a homography by LO-RANSAC, its eight motions, the one that explains the most rows.
+    -> (per-pair dicts: status (index into PLANE_STATUS), H (middle singular value 1), singular, h_inliers, iterations, motion_inliers (8),
+    chosen (-1 or 0 .. 7), R / t / rotation / translation / n_inliers of the chosen motion; mask (uint8 per row: bit 0 inlier of H, bit 1
+    inlier of the chosen motion); kernel milliseconds)."""
+    ctx = ctx or default_context()
+    b1 = np.ascontiguousarray(b1, np.float64).reshape(-1, 3)
+    b2 = np.ascontiguousarray(b2, np.float64).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(b1) != len(b2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(b1)):
+        raise ValueError("two_view_plane_pairs: b1 / b2 / offsets do not agree")
+    prm = _plane_params(threshold, iterations, probability, use_lo, lo_iterations, use_iteration_reduction)
+    res = (PlaneResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(b1), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_two_view_plane_pairs(ctx.handle, _fptr(b1, C.c_double), _fptr(b2, C.c_double), _fptr(off, C.c_int64), n_pairs, C.byref(prm),
+                                           res, _fptr(mask, C.c_uint8), C.byref(ms)), "osfm_two_view_plane_pairs")
+    return _plane_results(res, n_pairs), mask[: len(b1)], ms.value
+
+
+def two_view_plane_pairs_pixels(p1: np.ndarray, p2: np.ndarray, offsets: Sequence[int], pair_cams: np.ndarray, cam_model: np.ndarray,
+                                cam_params: np.ndarray, threshold: float, *, iterations: int = 1000, probability: float = 0.99,
+                                use_lo: bool = True, lo_iterations: int = 10, use_iteration_reduction: bool = True,
+                                ctx=None) -> Tuple[List[Dict[str, Any]], np.ndarray, float]:
+    """``osfm_two_view_plane_pairs_pixels``: the same from normalised image coordinates, the bearings computed on the device with the
+    cameras pair_cams[p] = (camera of side 1, camera of side 2) of the table cam_model (n_cams) / cam_params (n_cams x 16)."""
+    ctx = ctx or default_context()
+    p1 = np.ascontiguousarray(np.asarray(p1, np.float64).reshape(len(p1), -1)[:, :2])
+    p2 = np.ascontiguousarray(np.asarray(p2, np.float64).reshape(len(p2), -1)[:, :2])
+    off = np.ascontiguousarray(offsets, np.int64)
+    n_pairs = len(off) - 1
+    if len(p1) != len(p2) or n_pairs < 0 or (n_pairs > 0 and off[-1] != len(p1)):
+        raise ValueError("two_view_plane_pairs_pixels: p1 / p2 / offsets do not agree")
+    pc = np.ascontiguousarray(pair_cams, np.int32)
+    cm = np.ascontiguousarray(cam_model, np.int32)
+    cp = np.ascontiguousarray(cam_params, np.float64)
+    if pc.shape != (n_pairs, 2) or cm.ndim != 1 or cp.shape != (len(cm), 16):
+        raise ValueError(f"two_view_plane_pairs_pixels: pair_cams must be ({n_pairs}, 2) and cam_params ({len(cm)}, 16) for cam_model of length "
+                         f"{len(cm)}; got {pc.shape}, {cp.shape}")
+    prm = _plane_params(threshold, iterations, probability, use_lo, lo_iterations, use_iteration_reduction)
+    res = (PlaneResult * max(n_pairs, 1))()
+    mask = np.zeros(max(len(p1), 1), np.uint8)
+    ms = C.c_double(0.0)
+    check(load().osfm_two_view_plane_pairs_pixels(ctx.handle, _fptr(p1, C.c_double), _fptr(p2, C.c_double), _fptr(off, C.c_int64), n_pairs,
+                                                  _fptr(pc, C.c_int32), _fptr(cm, C.c_int32), _fptr(cp, C.c_double), len(cm), C.byref(prm), res,
+                                                  _fptr(mask, C.c_uint8), C.byref(ms)), "osfm_two_view_plane_pairs_pixels")
+    return _plane_results(res, n_pairs), mask[: len(p1)], ms.value
+
+
+def motion_from_plane_homography(H: np.ndarray, ctx=None) -> Optional[List[Tuple[np.ndarray, np.ndarray, np.ndarray, float]]]:
+    """Candidate camera motions from a plane-induced homography (``multiview.py:366-441``): eight (R, t, n, d), or None where two singular
+    values are nearly equal.  The signs of the singular vectors are fixed (plane_core.h), so the order is a property of H alone."""
+    ctx = ctx or default_context()
+    H = np.ascontiguousarray(H, np.float64).reshape(9)
+    motions = np.zeros((8, 16))
+    count = C.c_int(0)
+    check(load().osfm_plane_motions(ctx.handle, _fptr(H, C.c_double), _fptr(motions, C.c_double), C.byref(count)), "osfm_plane_motions")
+    if count.value == 0:
+        return None
+    return [(m[:9].reshape(3, 3).copy(), m[9:12].copy(), m[12:15].copy(), float(m[15])) for m in motions]
+
+
+def two_view_reconstruction_plane_based(b1: np.ndarray, b2: np.ndarray, threshold: float,
+                                        ctx=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Any]:
+    """Reconstruct two views from point correspondences lying on a plane (``reconstruction.py:298-333``): same arguments, same return --
+    (rotation vector, translation, inlier indices), or (None, None, []) without a homography or with a degenerate one.  The motion
+    returned is the one with the most inliers (the reference's ``np.argmax`` over a map object always takes the first)."""
+    res, mask, _ = two_view_plane_pairs(b1, b2, [0, len(b1)], threshold, ctx=ctx)
+    if res[0]["status"] != 0:
+        return None, None, []
+    return res[0]["rotation"], res[0]["translation"], np.flatnonzero(mask >> 1 & 1)
+
+
 def two_view_reconstruction_general_pairs(pairs: Sequence[Tuple[Any, Any, Any, Any]], threshold: float, iterations: int,
                                           check_reversal: bool = False, reversal_ratio: float = 1.0, *,
-                                          plane_based: Optional[Callable] = None, ctx=None) -> List[Tuple[Any, Any, Any, Dict[str, Any]]]:
+                                          plane_based=None, ctx=None) -> List[Tuple[Any, Any, Any, Dict[str, Any]]]:
     """``two_view_reconstruction_general`` (``reconstruction.py:488-560``) for a list of (p1, p2, camera1, camera2) in ONE GPU call: the
     bearings, the 5-point LO-RANSAC, both configurations and the choice.  -> [(R, t, inliers, report)] as the reference returns them.
-    The plane-based branch (``cv2.findHomography``) is not on the GPU: ``plane_based(b1, b2, threshold) -> (R, t, inliers)`` may supply it
-    (the reference's own ``two_view_reconstruction_plane_based`` fits) and is then compared as the reference compares; without it that
-    branch counts as not valid with 0 inliers."""
+    The plane-based branch: ``plane_based="device"`` runs it for the whole list in one more GPU call (``two_view_plane_pairs_pixels``);
+    a callable ``plane_based(b1, b2, threshold) -> (R, t, inliers)`` supplies it per pair on the host (the reference's own
+    ``two_view_reconstruction_plane_based`` fits); either is then compared as the reference compares.  Without the argument that branch
+    counts as not valid with 0 inliers."""
     from . import matching
 
     if not pairs:
@@ -878,12 +980,21 @@ def two_view_reconstruction_general_pairs(pairs: Sequence[Tuple[Any, Any, Any, A
     res, mask, _ = two_view_pairs_pixels(p1, p2, off, pair_cams, np.array(models, np.int32), np.array(params, np.float64).reshape(-1, 16), threshold,
                                          refine_iterations=iterations, check_reversal=check_reversal, reversal_ratio=reversal_ratio, iterations=1000,
                                          probability=0.99, ctx=ctx)
+    if isinstance(plane_based, str):
+        if plane_based != "device":
+            raise ValueError('two_view_reconstruction_general_pairs: plane_based must be None, a callable or "device"')
+        res_plane, mask_plane, _ = two_view_plane_pairs_pixels(p1, p2, off, pair_cams, np.array(models, np.int32),
+                                                               np.array(params, np.float64).reshape(-1, 16), threshold, ctx=ctx)
     out = []
     for k, (q1, q2, camera1, camera2) in enumerate(pairs):
         valid_5pt = res[k]["status"] == 0
         inliers_5p = np.flatnonzero(mask[off[k]: off[k + 1]] >> 2 & 1) if valid_5pt else []
         R_plane, t_plane, inliers_plane = None, None, []
-        if plane_based is not None:
+        if isinstance(plane_based, str):
+            if res_plane[k]["status"] == 0:
+                R_plane, t_plane = res_plane[k]["rotation"], res_plane[k]["translation"]
+                inliers_plane = np.flatnonzero(mask_plane[off[k]: off[k + 1]] >> 1 & 1)
+        elif plane_based is not None:
             R_plane, t_plane, inliers_plane = plane_based(matching.pixel_bearing_many(camera1, q1, ctx), matching.pixel_bearing_many(camera2, q2, ctx),
                                                           threshold)
         valid_plane = R_plane is not None and t_plane is not None
@@ -901,7 +1012,7 @@ def two_view_reconstruction_general_pairs(pairs: Sequence[Tuple[Any, Any, Any, A
 
 
 def two_view_reconstruction_general(p1: np.ndarray, p2: np.ndarray, camera1, camera2, threshold: float, iterations: int,
-                                    check_reversal: bool = False, reversal_ratio: float = 1.0, *, plane_based: Optional[Callable] = None,
+                                    check_reversal: bool = False, reversal_ratio: float = 1.0, *, plane_based=None,
                                     ctx=None) -> Tuple[Any, Any, Any, Dict[str, Any]]:
     """Reconstruct two views from point correspondences (``reconstruction.py:488-560``): same arguments, same return
     (rotation vector, translation, inliers, report).  See two_view_reconstruction_general_pairs for `plane_based`."""
