@@ -102,6 +102,9 @@ typedef struct {
                                       the fan-in of matching.py:83-98 across ranks) reads them from there.  osfm_result_fetch still
                                       works (one D2H copy on demand).                                                           */
 
+#define OSFM_MATCH_SWEEP_32X32 8   /* cross-check: the integer store's fused kernel on v_mfma_i32_32x32x32_i8 (the kernel the float
+                                      store runs) instead of the default v_mfma_i32_16x16x64_i8 sweep; same results             */
+
 void osfm_match_params_default(osfm_match_params *p);
 
 typedef struct {

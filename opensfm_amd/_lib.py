@@ -467,6 +467,7 @@ MAX_FEATURES = 16000     # OSFM_MAX_FEATURES
 MATCH_EXACT_KERNEL = 1   # OSFM_MATCH_EXACT_KERNEL
 MATCH_SQUARED_RATIO = 2  # OSFM_MATCH_SQUARED_RATIO
 MATCH_KEEP_DEVICE = 4    # OSFM_MATCH_KEEP_DEVICE
+MATCH_SWEEP_32X32 = 8    # OSFM_MATCH_SWEEP_32X32
 
 
 class Context:

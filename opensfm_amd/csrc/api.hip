@@ -485,17 +485,17 @@ static int match_pairs_impl(osfm_ctx *ctx, const osfm_store *store, const int32_
     } else if (params->flags & OSFM_MATCH_EXACT_KERNEL) {
       // debug/cross-check mode: every pair on the exact VALU kernel
       OSFM_HIP(hipMemsetAsync(S.flags.p, 0, (size_t)np * sizeof(int32_t), stA));
-      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, (params->flags & OSFM_MATCH_SQUARED_RATIO) ? 1 : 0, cap,
+      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, params->flags, cap,
                              S.counts.as<int32_t>(), S.matches.as<uint32_t>(), nullptr, true, stA);
       if (rc != OSFM_OK) return rc;
       OSFM_HIP(hipEventRecord(S.m1, stA));
     } else {
-      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, (params->flags & OSFM_MATCH_SQUARED_RATIO) ? 1 : 0, cap,
+      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, params->flags, cap,
                              S.counts.as<int32_t>(), S.matches.as<uint32_t>(), S.flags.as<int32_t>(), false, stA);
       if (rc != OSFM_OK) return rc;
       OSFM_HIP(hipEventRecord(S.m1, stA));
       // rare exact path: pairs whose second-nearest d^2 >= 2^22 (sqrtf is not injective there)
-      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, (params->flags & OSFM_MATCH_SQUARED_RATIO) ? 1 : 0, cap,
+      rc = osfm_launch_match(ctx, store, S.pairs.as<int32_t>(), np, params->lowes_ratio, params->symmetric, params->flags, cap,
                              S.counts.as<int32_t>(), S.matches.as<uint32_t>(), S.flags.as<int32_t>(), true, stA);
       if (rc != OSFM_OK) return rc;
     }

@@ -4,7 +4,7 @@
 set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-SRCS="api.hip match.hip ransac.hip ba.hip tracks.hip relpose.hip twoview.hip plane.hip relrot.hip abspose.hip cloud.hip triangulate.hip depthmap.hip prune.hip undistort.hip calib.hip guided.hip words.hip hahog.hip"
+SRCS="api.hip match.hip match16.hip ransac.hip ba.hip tracks.hip relpose.hip twoview.hip plane.hip relrot.hip abspose.hip cloud.hip triangulate.hip depthmap.hip prune.hip undistort.hip calib.hip guided.hip words.hip hahog.hip"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function $EXTRA_HIPCC_FLAGS"
 mkdir -p build
 echo "$FLAGS" > build/.flags.new

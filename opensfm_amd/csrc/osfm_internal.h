@@ -352,7 +352,7 @@ struct OsfmPerDeviceOnce {
 
 // match.hip
 int osfm_launch_match(osfm_ctx *ctx, const osfm_store *store, const int32_t *d_pairs, int64_t n_pairs,
-                      double ratio, int symmetric, int squared_ratio, int cap, int32_t *d_counts, uint32_t *d_matches,
+                      double ratio, int symmetric, int flags /* OSFM_MATCH_* */, int cap, int32_t *d_counts, uint32_t *d_matches,
                       int32_t *d_flags, bool exact_kernel, hipStream_t stream);
 // relpose.hip: the LO-RANSAC rounds (+ refinement in MATCH mode) over device-resident bearings; fills d_mask and d_out
 int osfm_relpose_run_device(osfm_ctx *ctx, hipStream_t st, const double *d_b1, const double *d_b2, const int64_t *d_off, const int64_t *offsets,

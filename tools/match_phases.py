@@ -2,6 +2,8 @@
 resident grid, what lies between two pairs of a workgroup and how long a workgroup lives (a build from before the resident grid
 reports neither: there a workgroup was a pair, and what it spent outside its buckets -- launch, header loads, LDS clear -- is the
 kernel time times the workgroup slots over the pairs, minus "whole pair").
+The ticks are in match.hip only: the tool runs the integer store on match_fused_kernel<false> (OSFM_MATCH_SWEEP_32X32), not on the default
+16x16x64 kernel of match16.hip, whose code around the step is the same.
 Needs the instrumented build (tools/libosfm_dbg_phases.so: match.hip compiled with -DOSFM_DBG_PHASES, linked with the product's
 other objects);  OSFM_MI355_LIB=tools/libosfm_dbg_phases.so python tools/match_phases.py"""
 import ctypes as C
@@ -27,7 +29,14 @@ def phases(lib, reset=True):
     return np.array(out[:], np.float64)
 
 
+def _sweep32_params(config=None, robust=True, _make=matching.make_params):
+    p = _make(config, robust)
+    p.flags |= _lib.MATCH_SWEEP_32X32  # the instrumented kernel
+    return p
+
+
 def main():
+    matching.make_params = _sweep32_params
     ctx = default_context(0)
     lib = _lib.load()
     scene = synthetic.make_matching_scene(1000, 2000, seed=0)
